@@ -14,6 +14,12 @@ world_size > 1 (weak scaling: per-GPU work fixed).
 Launch (driver contract):
   python bench.py --gpus N --steps K --warmup W
   torchrun --nnodes=1 --nproc-per-node N bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: set up, warm up, time
+--steps updates, print one JSON result line.  --dump-outputs DIR also writes
+what the last timed update computed as DIR/<name>.npy; inputs and seeds are
+fixed, so two builds run with the same arguments can be compared array for
+array.  --full is reserved for secondary measurements (none exist yet).
 """
 from __future__ import annotations
 
@@ -35,6 +41,79 @@ N_ENVS = 4096
 ROLLOUT_T = 128
 SYN_ROWS = 262_144  # ~6 months of 1-minute bars
 FEATURES = ["OPEN", "HIGH", "LOW", "CLOSE", "VOLUME", "FEAT_0", "FEAT_1", "FEAT_2"]
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs writes at most this much
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(trainer: PPOTrainer, out_dir: str) -> None:
+    """Write what the last timed step left in the trainer — the arrays a
+    caller of collect_rollout()/update() reads back — as float32 .npy files.
+
+    Small state (parameters, Adam moments, bootstrap value) is written
+    whole.  The loss sums are left out: the timed path runs
+    update(with_stats=False) and never reads them, and they are logging-only
+    atomic float sums whose low bits depend on block order.  The per-(t, env)
+    rollout arrays are written whole while they fit the byte budget; beyond
+    it a fixed seeded sample of (t, env) rows is taken, the same rows for
+    every array, and the row indices are written next to them so two builds
+    can be compared row for row.
+    """
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    T, N, D = trainer.T, trainer.N, trainer.D
+    TN = T * N
+
+    def host(t: torch.Tensor) -> "np.ndarray":
+        return t.detach().to(torch.float32).cpu().numpy()
+
+    model = trainer.model
+    whole = {
+        "params": model.params,
+        "adam_m": model.m,
+        "adam_v": model.v,
+        "bootstrap_value": trainer.val_buf[T],
+    }
+    per_row = {  # [T, N] -> one scalar per (t, env) row
+        "actions": trainer.act_buf,
+        "logp": trainer.logp_buf,
+        "values": trainer.val_buf[:T],
+        "rewards": trainer.rew_buf,
+        "dones": trainer.done_buf,
+        "advantages": trainer.adv_buf,
+        "returns": trainer.ret_buf,
+    }
+    budget = DUMP_BUDGET_BYTES - 4 * sum(t.numel() for t in whole.values())
+    rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+
+    def pick_rows(row_bytes: int, share: int):
+        """All TN rows when they fit `share` bytes, else a sorted seeded
+        sample; the index array itself (float64) is charged to the share."""
+        if TN * row_bytes <= share:
+            return None
+        k = max(1, share // (row_bytes + 8))
+        return np.sort(rng.choice(TN, size=k, replace=False))
+
+    # scalar-per-row arrays get a third of the budget (whole at the flagship
+    # shape), observations the rest
+    rows_small = pick_rows(4 * len(per_row), budget // 3)
+    rows_obs = pick_rows(4 * D, budget - budget // 3)
+
+    for name, t in whole.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), host(t))
+    for name, t in per_row.items():
+        flat = t.reshape(TN)
+        if rows_small is not None:
+            flat = flat[torch.from_numpy(rows_small).to(flat.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), host(flat))
+    obs = trainer.obs_flat
+    if rows_obs is not None:
+        obs = obs[torch.from_numpy(rows_obs).to(obs.device)]
+    np.save(os.path.join(out_dir, "obs.npy"), host(obs))
+    # which (t, env) rows the files above hold: row = t * n_envs + env
+    for name, rows in (("rows_small", rows_small), ("rows_obs", rows_obs)):
+        if rows is not None:
+            np.save(os.path.join(out_dir, f"{name}.npy"), rows.astype(np.float64))
 
 
 def main() -> None:
@@ -53,7 +132,18 @@ def main() -> None:
                     help="strategy plugin (default: BASELINE config for the run shape)")
     ap.add_argument("--pairs", type=int, default=1,
                     help="instruments in the market tensor (BASELINE config #5)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step "
+                         "computed (rollout slabs, advantages, parameters, "
+                         "Adam moments) as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the benchmark's secondary measurements. "
+                         "A plain run only sets up, warms up, times --steps "
+                         "updates and prints the result line; there are no "
+                         "secondary measurements yet, so this changes nothing")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -178,6 +268,9 @@ def main() -> None:
     total_env_steps = args.steps * env_steps_per_update * world_size
     value = total_env_steps / elapsed
     ms_per_step = elapsed / args.steps * 1000.0
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(trainer, args.dump_outputs)
 
     if rank == 0:
         print(json.dumps({
