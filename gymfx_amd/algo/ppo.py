@@ -72,6 +72,16 @@ class PPOConfig:
                                   # splits bandwidth and adds event-sync
                                   # overhead.  Kept with a bit-equality
                                   # GPU test, like fused_rollout.
+    fused_opt_tail: bool = True  # per-minibatch reduce/optimizer tail in
+                                 # 3 launches instead of 13: one
+                                 # grads_finalize (all slab reduces + grad-
+                                 # norm partials), one Adam that also writes
+                                 # the transposed weight mirrors and
+                                 # advances adam_ctr; the mb_ctr increment
+                                 # stays.  Bitwise == the unfused sequence
+                                 # (tests/test_gpu_opt_tail.py); +2.7 % on
+                                 # the MLP headline.  MLP only: measured
+                                 # slower on the LSTM (PERF_NOTES.md).
 
     @classmethod
     def from_config(cls, cfg: Dict[str, Any]) -> "PPOConfig":
@@ -98,6 +108,7 @@ class PPOConfig:
             "fuse_sample": "fuse_sample",
             "fuse_head": "fuse_head",
             "overlap_gather": "overlap_gather",
+            "fused_opt_tail": "fused_opt_tail",
         }
         from ..config.merger import convert_type
 
@@ -252,6 +263,31 @@ class PPOTrainer:
         self._fm = {"seed": self.shuffle_seed, "minibatches": cfg.minibatches,
                     "ctr_off": -1, "step_base": self.step_base,
                     "mb_ctr": self.mb_ctr}
+
+        # fused optimizer tail: the norm partials come out of grads_finalize
+        # only when nothing rewrites grads before Adam (no all-reduce)
+        # LSTM: MEASURED NEGATIVE (update 35.24 -> 35.60 ms at 4096 envs:
+        # its 530k parameters walk grads_finalize's 65536-element stride
+        # nine times with a barrier pair each, slower than the wide
+        # per-layer reduces it replaces — profiles/PERF_NOTES.md).  The
+        # recurrent trainer keeps the unfused tail unless
+        # GYMFX_LSTM_OPT_TAIL=1; the bitwise GPU tests run it.
+        self._fused_tail = bool(cfg.fused_opt_tail) and (
+            not self.recurrent
+            or _os.environ.get("GYMFX_LSTM_OPT_TAIL", "0") == "1")
+        self.model.fused_tail = self._fused_tail
+        self.model.fuse_norm = (self._fused_tail and world_size <= 1
+                                and cfg.max_grad_norm > 0)
+        # ticket word of the in-kernel mb_ctr advance (ops/api.mb_gather).
+        # MEASURED NEGATIVE at the flagship shape: the gather launches one
+        # block per 4 rows (16384 blocks), and 16384 draws on one word took
+        # the kernel from 36.6 to 544 us (profiles/PERF_NOTES.md) — far
+        # more than the 4 us increment launch it removes.  Opt-in via
+        # GYMFX_GATHER_TICKET=1; the bitwise GPU test keeps the path honest.
+        self._mb_ticket = (
+            torch.zeros((), dtype=torch.int32, device=dev)
+            if self._fused_tail
+            and _os.environ.get("GYMFX_GATHER_TICKET", "0") == "1" else None)
 
         self.global_step = 0   # host mirror of step_base (logging/ckpt)
         self.update_count = 0
@@ -412,7 +448,7 @@ class PPOTrainer:
                 self.ret_mb, self.done_mb, self.h0_mb, self.c0_mb,
                 L=cfg.bptt_len, seed=self.shuffle_seed,
                 minibatches=cfg.minibatches, step_base=self.step_base,
-                mb_ctr=self.mb_ctr,
+                mb_ctr=self.mb_ctr, ticket=self._mb_ticket,
             )
         else:
             api.mb_gather(
@@ -421,9 +457,10 @@ class PPOTrainer:
                 self.logp_mb_s[slot], self.adv_mb_s[slot], self.ret_mb_s[slot],
                 seed=self.shuffle_seed, minibatches=cfg.minibatches,
                 step_base=self.step_base, mb_ctr=self.mb_ctr,
-                skip_obs=self._fuse_gather,
+                skip_obs=self._fuse_gather, ticket=self._mb_ticket,
             )
-        api.increment_counter(self.mb_ctr, 1)
+        if self._mb_ticket is None:
+            api.increment_counter(self.mb_ctr, 1)
 
     def _fwd_bwd_body(self, slot: int = 0) -> None:
         """Forward + PPO loss backward + model backward on the gathered

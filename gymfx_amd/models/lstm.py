@@ -100,6 +100,11 @@ class ActorCriticLSTM:
         self._clip_scale = torch.ones(1, dtype=torch.float32, device=device)
         self._wg_ws: Dict[str, Tuple[torch.Tensor, Optional[torch.Tensor], int]] = {}
         self.wgrad_slabs = 64
+        # fused optimizer tail — same contract as models/mlp.py
+        self.fused_tail = False
+        self.fuse_norm = False
+        self._adam_ticket = torch.zeros((), dtype=torch.int32, device=device)
+        self._fin_segs = None
 
     # -- param views ----------------------------------------------------
     def w(self, name: str) -> torch.Tensor:
@@ -132,6 +137,20 @@ class ActorCriticLSTM:
         while tiles * s < 2048:
             s *= 2
         return s
+
+    def _finalize_segments(self):
+        """(workspace, elems, slabs, flat offset, is_bias) per gradient
+        slice, from the workspaces bptt_backward() has just filled."""
+        if self._fin_segs is None:
+            segs = []
+            for (wn, bn) in (("Wy", "by"), ("Wx", "b"), ("Wh", None)):
+                K, N = self.slices[wn].shape
+                dw, db, S = self._wg_ws[f"{wn}:{K}x{N}"]
+                segs.append((dw, K * N, S, self.slices[wn].sl.start, False))
+                if bn is not None:
+                    segs.append((db, N, S, self.slices[bn].sl.start, True))
+            self._fin_segs = segs
+        return self._fin_segs
 
     def _wg_workspace(self, name: str, K: int, N: int, want_db: bool):
         key = f"{name}:{K}x{N}"
@@ -256,10 +275,11 @@ class ActorCriticLSTM:
         L, M, D = obs_seq.shape
         H = self.hidden
         h_raw_flat = buf["h_raw"].view(L * M, H)
+        red = not self.fused_tail  # fused tail: one grads_finalize at the end
         # head layer
         dw_p, db_p, slabs = self._wg_workspace("Wy", H, self.head_dim, True)
         api.wgrad(h_raw_flat, dhead, self.grad("Wy"), self.grad("by"),
-                  workspace=(dw_p, db_p), slabs=slabs)
+                  workspace=(dw_p, db_p), slabs=slabs, reduce=red)
         dh_flat = buf["dh_all"].view(L * M, H)
         api.gemm(dhead, self.w("Wy"), None, dh_flat, act=1, trans_b=True)
         # backward through time: ONE fused kernel per step computes dgates
@@ -282,10 +302,15 @@ class ActorCriticLSTM:
         dgates_flat = buf["dgates"].view(L * M, 4 * H)
         dw_p, db_p, slabs = self._wg_workspace("Wx", D, 4 * H, True)
         api.wgrad(obs_seq.view(L * M, D), dgates_flat, self.grad("Wx"),
-                  self.grad("b"), workspace=(dw_p, db_p), slabs=slabs)
+                  self.grad("b"), workspace=(dw_p, db_p), slabs=slabs,
+                  reduce=red)
         dw_p, db_p, slabs = self._wg_workspace("Wh", H, 4 * H, False)
         api.wgrad(buf["h_in"][:L].reshape(L * M, H), dgates_flat,
-                  self.grad("Wh"), None, workspace=(dw_p, db_p), slabs=slabs)
+                  self.grad("Wh"), None, workspace=(dw_p, db_p), slabs=slabs,
+                  reduce=red)
+        if self.fused_tail:
+            api.grads_finalize(self._finalize_segments(), self.grads,
+                               self._clip_part if self.fuse_norm else None)
 
     # -- optimizer --------------------------------------------------------
     def adam(self, lr: float, *, beta1=0.9, beta2=0.999, eps=1e-8,
@@ -296,6 +321,15 @@ class ActorCriticLSTM:
             # fused clipping: sumsq partials + per-block scale derivation
             # inside the adam launch (no separate clip_scale kernel)
             clip = (self._clip_part, max_grad_norm)
+        if self.fused_tail:
+            api.adam_tail(self.params, self.grads, self.m, self.v,
+                          self.params_bf16, lr=lr, beta1=beta1, beta2=beta2,
+                          eps=eps, step_ctr=self.adam_ctr,
+                          ticket=self._adam_ticket, clip=clip,
+                          sumsq_done=self.fuse_norm,
+                          mirrors=[(self.slices[n].sl.start, t)
+                                   for n, t in self._wt.items()])
+            return
         api.adam(self.params, self.grads, self.m, self.v, self.params_bf16,
                  lr=lr, beta1=beta1, beta2=beta2, eps=eps, step=self.adam_step,
                  step_ctr=self.adam_ctr, clip=clip)

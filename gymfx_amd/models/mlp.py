@@ -91,6 +91,16 @@ class ActorCriticMLP:
         # wgrad slab workspaces (allocated lazily per layer shape)
         self._wg_ws: Dict[str, Tuple[torch.Tensor, Optional[torch.Tensor]]] = {}
         self.wgrad_slabs = 64
+        # fused optimizer tail (PPOConfig.fused_opt_tail): backward() ends
+        # in ONE grads_finalize launch instead of six slab reduces, and
+        # adam() is ONE launch that also writes the transposed mirrors and
+        # advances adam_ctr.  fuse_norm: finalize also writes the grad-norm
+        # partials (only valid when nothing touches grads between backward
+        # and adam, i.e. no gradient all-reduce).
+        self.fused_tail = False
+        self.fuse_norm = False
+        self._adam_ticket = torch.zeros((), dtype=torch.int32, device=device)
+        self._fin_segs = None
 
     # -- param views ----------------------------------------------------
     def w(self, name: str) -> torch.Tensor:
@@ -125,6 +135,19 @@ class ActorCriticMLP:
         while tiles * s < 2048:
             s *= 2
         return s
+
+    def _finalize_segments(self):
+        """(workspace, elems, slabs, flat offset, is_bias) per gradient
+        slice, from the workspaces backward() has just filled."""
+        if self._fin_segs is None:
+            segs = []
+            for (wn, bn) in (("W3", "b3"), ("W2", "b2"), ("W1", "b1")):
+                K, N = self.slices[wn].shape
+                dw, db, S = self._wg_ws[f"{wn}:{K}x{N}"]
+                segs.append((dw, K * N, S, self.slices[wn].sl.start, False))
+                segs.append((db, N, S, self.slices[bn].sl.start, True))
+            self._fin_segs = segs
+        return self._fin_segs
 
     def _wg_workspace(self, name: str, K: int, N: int, want_db: bool):
         key = f"{name}:{K}x{N}"
@@ -191,22 +214,29 @@ class ActorCriticMLP:
         M = dhead.shape[0]
         dh2 = scratch["dh2"]
         dh1 = scratch["dh1"]
+        # fused tail: the wgrads only fill their slab workspaces; one
+        # grads_finalize launch at the end reduces all six slices
+        red = not self.fused_tail
         # head layer
         dw_p, db_p, slabs = self._wg_workspace("W3", self.hidden, self.head_dim, True)
         api.wgrad(acts["h2"], dhead, self.grad("W3"), self.grad("b3"),
-                  workspace=(dw_p, db_p), slabs=slabs)
+                  workspace=(dw_p, db_p), slabs=slabs, reduce=red)
         api.gemm(dhead, self.w("W3"), None, dh2, Yact=acts["h2"], trans_b=True,
                  act=1, dact_tanh=True)
         # layer 2
         dw_p, db_p, slabs = self._wg_workspace("W2", self.hidden, self.hidden, True)
         api.wgrad(acts["h1"], dh2, self.grad("W2"), self.grad("b2"),
-                  workspace=(dw_p, db_p), slabs=slabs)
+                  workspace=(dw_p, db_p), slabs=slabs, reduce=red)
         api.gemm(dh2, self.w("W2"), None, dh1, Yact=acts["h1"], trans_b=True,
                  act=1, dact_tanh=True)
         # layer 1
         dw_p, db_p, slabs = self._wg_workspace("W1", self.obs_dim, self.hidden, True)
         api.wgrad(obs_bf16, dh1, self.grad("W1"), self.grad("b1"),
-                  workspace=(dw_p, db_p), slabs=slabs, x_perm=a_feistel)
+                  workspace=(dw_p, db_p), slabs=slabs, x_perm=a_feistel,
+                  reduce=red)
+        if self.fused_tail:
+            api.grads_finalize(self._finalize_segments(), self.grads,
+                               self._clip_part if self.fuse_norm else None)
 
     def alloc_scratch(self, M: int) -> Dict[str, torch.Tensor]:
         dev = self.device
@@ -224,6 +254,15 @@ class ActorCriticMLP:
             # fused clipping: sumsq partials + per-block scale derivation
             # inside the adam launch (no separate clip_scale kernel)
             clip = (self._clip_part, max_grad_norm)
+        if self.fused_tail:
+            api.adam_tail(self.params, self.grads, self.m, self.v,
+                          self.params_bf16, lr=lr, beta1=beta1, beta2=beta2,
+                          eps=eps, step_ctr=self.adam_ctr,
+                          ticket=self._adam_ticket, clip=clip,
+                          sumsq_done=self.fuse_norm,
+                          mirrors=[(self.slices[n].sl.start, t)
+                                   for n, t in self._wt.items()])
+            return
         # bias correction reads the DEVICE counter (graph-replayable); the
         # host step is a fallback for paths that pass step_ctr=None.
         api.adam(self.params, self.grads, self.m, self.v, self.params_bf16,

@@ -6,7 +6,7 @@ matches them.  On a CUDA/ROCm device the native extension is required
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple
 
 import os
 
@@ -278,9 +278,14 @@ def wgrad(
     workspace: Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]] = None,
     slabs: int = 64,
     x_perm: "Optional[dict]" = None,
+    reduce: bool = True,
 ) -> None:
     """dW[K,N] = X^T @ dY ; db[N] = colsum(dY). Deterministic split-M.
-    x_perm: same contract as gemm's a_perm (X rows via the permutation)."""
+    x_perm: same contract as gemm's a_perm (X rows via the permutation).
+    reduce=False (GPU): only the slab partials are written into
+    ``workspace``; dW/db are left for ``grads_finalize``, which reduces
+    every layer's workspace in one launch.  The CPU oracle has no slabs: it
+    always writes dW/db, and ``grads_finalize`` is then the identity."""
     if _use_native(X):
         K, N = dW.shape
         if workspace is None:
@@ -298,9 +303,10 @@ def wgrad(
                                    ap_minibatches=x_perm["minibatches"],
                                    ap_ctr_off=x_perm.get("ctr_off", 0),
                                    ap_step_base=x_perm["step_base"],
-                                   ap_mb_ctr=x_perm["mb_ctr"])
+                                   ap_mb_ctr=x_perm["mb_ctr"], reduce=reduce)
             return
-        native.require().wgrad(X, dY, dW_part, db_part, dW, db, slabs)
+        native.require().wgrad(X, dY, dW_part, db_part, dW, db, slabs,
+                               reduce=reduce)
         return
     if x_perm is not None:
         X = X[_perm_rows(X.shape[0], dY.shape[0], x_perm)]
@@ -309,6 +315,29 @@ def wgrad(
     dW.copy_(x.t() @ dy)
     if db is not None:
         db.copy_(dy.sum(dim=0))
+
+
+def grads_finalize(
+    segments: "Sequence[Tuple[torch.Tensor, int, int, int, bool]]",
+    grads: torch.Tensor,
+    clip_part: Optional[torch.Tensor] = None,
+) -> None:
+    """Reduce the slab workspaces that ``wgrad(..., reduce=False)`` filled
+    into the flat ``grads`` buffer, all in ONE launch.  A segment is
+    ``(workspace, elems, slabs, offset, is_bias)``: ``workspace`` holds
+    ``[slabs, elems]`` partials and the sums land in
+    ``grads[offset:offset + elems]``, bit for bit what the per-layer reduce
+    kernels of ``wgrad`` would write.  ``clip_part`` (256 floats): the
+    kernel also writes the sum-of-squares partials of the whole buffer, the
+    values the sumsq launch of ``adam(clip=...)`` computes (pass
+    ``sumsq_done=True`` to ``adam_tail`` then)."""
+    if _use_native(grads):
+        native.require().grads_finalize(
+            [s[0] for s in segments], [int(s[1]) for s in segments],
+            [int(s[2]) for s in segments], [int(s[3]) for s in segments],
+            [bool(s[4]) for s in segments], grads, clip_part)
+        return
+    # CPU oracle: wgrad wrote dW/db itself and adam derives the norm from g
 
 
 def gae(
@@ -380,6 +409,46 @@ def adam(
     p.addcdiv_(mhat, vhat.sqrt() + eps, value=-lr)
     if p_bf16 is not None:
         p_bf16.copy_(p.to(torch.bfloat16))
+
+
+def adam_tail(
+    p: torch.Tensor,
+    g: torch.Tensor,
+    m: torch.Tensor,
+    v: torch.Tensor,
+    p_bf16: Optional[torch.Tensor],
+    *,
+    lr: float,
+    beta1: float = 0.9,
+    beta2: float = 0.999,
+    eps: float = 1e-8,
+    step_ctr: torch.Tensor,
+    ticket: Optional[torch.Tensor] = None,
+    clip: "Optional[Tuple[torch.Tensor, float]]" = None,
+    sumsq_done: bool = False,
+    mirrors: "Sequence[Tuple[int, torch.Tensor]]" = (),
+) -> None:
+    """``adam`` plus what used to follow it, in one launch: every
+    ``(offset, mirror[N,K])`` weight gets its transposed bf16 mirror written
+    by the Adam kernel itself (== ``transpose_bf16`` of the ``p_bf16``
+    slice), and with ``ticket`` (zero-initialised int32 scalar) the kernel
+    advances ``step_ctr`` by one (== ``increment_counter(step_ctr, 1)``).
+    sumsq_done: ``clip[0]`` already holds the partials (``grads_finalize``)."""
+    if _use_native(p):
+        part, max_norm = clip if clip is not None else (None, 0.0)
+        native.require().adam_tail(
+            p, g, m, v, p_bf16, lr, beta1, beta2, eps, step_ctr, ticket, part,
+            float(max_norm), sumsq_done, [int(o) for o, _ in mirrors],
+            [t for _, t in mirrors])
+        return
+    adam(p, g, m, v, p_bf16, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
+         step_ctr=step_ctr, clip=clip)
+    if ticket is not None:
+        increment_counter(step_ctr, 1)
+    for off, t in mirrors:
+        N, K = t.shape
+        src = (p_bf16 if p_bf16 is not None else p.to(torch.bfloat16))
+        transpose_bf16(src[off:off + K * N].view(K, N), t)
 
 
 def grad_clip_scale(
@@ -607,17 +676,20 @@ def mb_gather(
     step_base: torch.Tensor,
     mb_ctr: torch.Tensor,
     skip_obs: bool = False,
+    ticket: Optional[torch.Tensor] = None,
 ) -> None:
     """Gather minibatch ``mb_ctr % minibatches`` of epoch
     ``mb_ctr // minibatches`` under the Feistel permutation keyed by
     (seed, *step_base, epoch).  One fused kernel on GPU.  skip_obs: the
     gather+first-GEMM fusion reads obs through the permutation itself, so
-    only the small per-row fields are copied."""
+    only the small per-row fields are copied.  ticket (zero-initialised
+    int32 scalar): the gather kernel also advances ``mb_ctr`` by one once
+    every block has read it (no ``increment_counter`` launch after it)."""
     if _use_native(obs_src):
         native.require().mb_gather(
             obs_src, act_src, logp_src, adv_src, ret_src, obs_mb, act_mb,
             logp_mb, adv_mb, ret_mb, seed, minibatches, step_base, mb_ctr,
-            skip_obs,
+            skip_obs, ticket,
         )
         return
     n = obs_src.shape[0]
@@ -632,6 +704,8 @@ def mb_gather(
     logp_mb.copy_(logp_src[src])
     adv_mb.copy_(adv_src[src])
     ret_mb.copy_(ret_src[src])
+    if ticket is not None:
+        mb_ctr.add_(1)
 
 
 def mb_gather_seq(
@@ -657,10 +731,11 @@ def mb_gather_seq(
     minibatches: int,
     step_base: torch.Tensor,
     mb_ctr: torch.Tensor,
+    ticket: Optional[torch.Tensor] = None,
 ) -> None:
     """Recurrent-PPO sequence gather: minibatch of (chunk, env) sequences
     under the Feistel permutation, time-major output + chunk-boundary
-    recurrent state."""
+    recurrent state.  ticket: as in ``mb_gather``."""
     n_chunks, N, H = h0_src.shape
     if _use_native(obs_src):
         native.require().mb_gather_seq(
@@ -670,7 +745,7 @@ def mb_gather_seq(
             h0_src, c0_src, obs_mb.view(-1, obs_mb.shape[-1]),
             act_mb.view(-1), logp_mb.view(-1), adv_mb.view(-1),
             ret_mb.view(-1), done_mb.view(-1), h0_mb, c0_mb, L, N, seed,
-            minibatches, step_base, mb_ctr,
+            minibatches, step_base, mb_ctr, ticket,
         )
         return
     Mseq = c0_mb.shape[0]
@@ -691,6 +766,8 @@ def mb_gather_seq(
         adv_mb[li].copy_(adv_src[t, env])
         ret_mb[li].copy_(ret_src[t, env])
         done_mb[li].copy_(done_src[t, env])
+    if ticket is not None:
+        mb_ctr.add_(1)
 
 
 def increment_counter(ctr: torch.Tensor, delta: int) -> None:

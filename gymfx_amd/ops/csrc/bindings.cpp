@@ -62,11 +62,20 @@ void launch_mb_gather_seq(const void* obs_src, const int64_t* act_src,
                           int H, int N, uint32_t n_seq, int half,
                           uint64_t seed, int minibatches,
                           const unsigned long long* step_base,
-                          const unsigned long long* mb_ctr,
+                          unsigned long long* mb_ctr, unsigned int* ticket,
                           hipStream_t stream);
 void launch_wgrad(const void* X, const void* dY, float* dW_part, float* db_part,
                   float* dW, float* db, int M, int N, int K, int slabs,
-                  hipStream_t stream, const FeistelMap* fmp = nullptr);
+                  hipStream_t stream, const FeistelMap* fmp = nullptr,
+                  bool reduce = true);
+void launch_grads_finalize(const FinalizeTable& tab, float* grads, int64_t n,
+                           float* clip_part, hipStream_t stream);
+void launch_adam_tail(float* p, const float* g, float* m, float* v,
+                      void* p_bf16, int64_t n, float lr, float beta1,
+                      float beta2, float eps, int* step_ctr,
+                      unsigned int* ticket, const float* clip_part, int nparts,
+                      float max_norm, const MirrorTable& mt,
+                      hipStream_t stream);
 void launch_gae(const float* rewards, const float* values, const bool* dones,
                 float* adv, float* ret, int T, int N, float gamma, float lam,
                 hipStream_t stream);
@@ -105,8 +114,8 @@ void launch_mb_gather(const void* obs_src, const int64_t* act_src,
                       float* logp_mb, float* adv_mb, float* ret_mb, int M,
                       int D, uint32_t n, int half, uint64_t seed,
                       int minibatches, const unsigned long long* step_base,
-                      const unsigned long long* mb_ctr, hipStream_t stream,
-                      int skip_obs = 0);
+                      unsigned long long* mb_ctr, hipStream_t stream,
+                      int skip_obs = 0, unsigned int* ticket = nullptr);
 void launch_ppo_loss_bwd(const float* head, const int64_t* actions,
                          const float* old_logp, const float* adv,
                          const float* ret, void* dhead, int M, int n_actions,
@@ -510,6 +519,15 @@ void check_f32(const torch::Tensor& t, const char* name) {
               name, " must be contiguous f32");
 }
 
+// zero-initialised int32 ticket word of the last-block counter advance
+// (nullptr: the kernel leaves the counter alone)
+unsigned int* ticket_ptr(const c10::optional<torch::Tensor>& ticket) {
+  if (!ticket.has_value()) return nullptr;
+  TORCH_CHECK(ticket->scalar_type() == torch::kInt32 && ticket->numel() == 1,
+              "ticket must be a scalar int32 tensor");
+  return reinterpret_cast<unsigned int*>(ticket->data_ptr());
+}
+
 // build a FeistelMap from the python-side dict-args of the gather fusion
 static gymfx::FeistelMap make_fmap(int64_t n_rows, int M_mb, int64_t seed,
                                    int64_t minibatches, int64_t ctr_off,
@@ -749,7 +767,8 @@ void mb_gather_seq_op(torch::Tensor obs_src, torch::Tensor act_src,
                       torch::Tensor done_mb,
                       torch::Tensor h0_mb, torch::Tensor c0_mb, int64_t L,
                       int64_t N, int64_t seed, int64_t minibatches,
-                      torch::Tensor step_base, torch::Tensor mb_ctr) {
+                      torch::Tensor step_base, torch::Tensor mb_ctr,
+                      c10::optional<torch::Tensor> ticket) {
   check_bf16(obs_src, "obs_src");
   check_bf16(obs_mb, "obs_mb");
   check_bf16(h0_mb, "h0_mb");
@@ -777,8 +796,8 @@ void mb_gather_seq_op(torch::Tensor obs_src, torch::Tensor act_src,
       c0_mb.data_ptr<float>(), Mseq, (int)L, D, H, (int)N, (uint32_t)n_seq,
       bits / 2, (uint64_t)seed, (int)minibatches,
       reinterpret_cast<const unsigned long long*>(step_base.data_ptr()),
-      reinterpret_cast<const unsigned long long*>(mb_ctr.data_ptr()),
-      cur_stream());
+      reinterpret_cast<unsigned long long*>(mb_ctr.data_ptr()),
+      ticket_ptr(ticket), cur_stream());
 }
 
 
@@ -788,7 +807,7 @@ void wgrad_op(torch::Tensor X, torch::Tensor dY, torch::Tensor dW_part,
               c10::optional<torch::Tensor> db, int64_t slabs,
               int64_t ap_seed, int64_t ap_minibatches, int64_t ap_ctr_off,
               c10::optional<torch::Tensor> ap_step_base,
-              c10::optional<torch::Tensor> ap_mb_ctr) {
+              c10::optional<torch::Tensor> ap_mb_ctr, bool reduce) {
   check_bf16(X, "X");
   check_bf16(dY, "dY");
   check_f32(dW, "dW");
@@ -815,12 +834,58 @@ void wgrad_op(torch::Tensor X, torch::Tensor dY, torch::Tensor dW_part,
                                      ap_ctr_off, *ap_step_base, *ap_mb_ctr);
     gymfx::launch_wgrad(X.data_ptr(), dY.data_ptr(),
                         dW_part.data_ptr<float>(), dbp, dW.data_ptr<float>(),
-                        dbo, M, N, K, (int)slabs, cur_stream(), &fm);
+                        dbo, M, N, K, (int)slabs, cur_stream(), &fm, reduce);
     return;
   }
   gymfx::launch_wgrad(X.data_ptr(), dY.data_ptr(), dW_part.data_ptr<float>(),
                       dbp, dW.data_ptr<float>(), dbo, M, N, K, (int)slabs,
-                      cur_stream());
+                      cur_stream(), nullptr, reduce);
+}
+
+// One launch reduces every listed slab workspace into the flat gradient
+// buffer (segment s: parts[s] = [slabs[s], elems[s]] partials -> grads[
+// offs[s] : offs[s] + elems[s]]).  The association order per segment is the
+// one launch_wgrad's reduce dispatch picks: every bias and every weight of
+// at most 4096 elements the small tree, the rest the vector path.
+void grads_finalize_op(std::vector<torch::Tensor> parts,
+                       std::vector<int64_t> elems, std::vector<int64_t> slabs,
+                       std::vector<int64_t> offs, std::vector<bool> is_bias,
+                       torch::Tensor grads,
+                       c10::optional<torch::Tensor> clip_part) {
+  check_f32(grads, "grads");
+  const size_t ns = parts.size();
+  TORCH_CHECK(ns <= (size_t)gymfx::kMaxFinalizeSegs, "too many segments");
+  TORCH_CHECK(elems.size() == ns && slabs.size() == ns && offs.size() == ns &&
+                  is_bias.size() == ns,
+              "segment lists differ in length");
+  const int64_t n = grads.numel();
+  gymfx::FinalizeTable tab;
+  tab.nseg = (int)ns;
+  for (size_t s = 0; s < ns; ++s) {
+    check_f32(parts[s], "parts");
+    TORCH_CHECK(parts[s].device() == grads.device(), "parts device");
+    TORCH_CHECK(elems[s] > 0 && slabs[s] > 0 && slabs[s] < (1 << 30),
+                "bad segment size");
+    TORCH_CHECK(parts[s].numel() >= slabs[s] * elems[s], "parts too small");
+    TORCH_CHECK(offs[s] >= 0 && offs[s] + elems[s] <= n,
+                "segment outside grads");
+    for (size_t r = 0; r < s; ++r)
+      TORCH_CHECK(offs[s] >= offs[r] + elems[r] || offs[r] >= offs[s] + elems[s],
+                  "segments overlap");
+    tab.seg[s].part = parts[s].data_ptr<float>();
+    tab.seg[s].elems = elems[s];
+    tab.seg[s].off = offs[s];
+    tab.seg[s].slabs = (int)slabs[s];
+    tab.seg[s].small = (is_bias[s] || elems[s] <= 4096) ? 1 : 0;
+  }
+  float* cp = nullptr;
+  if (clip_part.has_value()) {
+    check_f32(*clip_part, "clip_part");
+    TORCH_CHECK(clip_part->numel() == 256, "clip_part must hold 256 partials");
+    cp = clip_part->data_ptr<float>();
+  }
+  gymfx::launch_grads_finalize(tab, grads.data_ptr<float>(), n, cp,
+                               cur_stream());
 }
 
 void gae_op(torch::Tensor rewards, torch::Tensor values, torch::Tensor dones,
@@ -882,6 +947,66 @@ void adam_op(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v,
                      m.data_ptr<float>(), v.data_ptr<float>(), pb, n, (float)lr,
                      (float)beta1, (float)beta2, (float)eps, bc1, bc2, gs, sc,
                      cur_stream());
+}
+
+// adam + transposed weight mirrors + step-counter advance in one launch.
+// sumsq_done: clip_part already holds the partials (grads_finalize wrote
+// them); otherwise the sumsq launch runs first, as in adam_op.
+void adam_tail_op(torch::Tensor p, torch::Tensor g, torch::Tensor m,
+                  torch::Tensor v, c10::optional<torch::Tensor> p_bf16,
+                  double lr, double beta1, double beta2, double eps,
+                  torch::Tensor step_ctr, c10::optional<torch::Tensor> ticket,
+                  c10::optional<torch::Tensor> clip_part, double clip_max_norm,
+                  bool sumsq_done, std::vector<int64_t> mirror_offs,
+                  std::vector<torch::Tensor> mirrors) {
+  check_f32(p, "p");
+  check_f32(g, "g");
+  check_f32(m, "m");
+  check_f32(v, "v");
+  const int64_t n = p.numel();
+  TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n);
+  void* pb = nullptr;
+  if (p_bf16.has_value()) {
+    check_bf16(*p_bf16, "p_bf16");
+    TORCH_CHECK(p_bf16->numel() == n, "p_bf16 numel");
+    pb = p_bf16->data_ptr();
+  }
+  TORCH_CHECK(step_ctr.scalar_type() == torch::kInt32 && step_ctr.numel() == 1,
+              "step_ctr int32 scalar");
+  const size_t ns = mirrors.size();
+  TORCH_CHECK(ns <= (size_t)gymfx::kMaxMirrorSegs && mirror_offs.size() == ns,
+              "bad mirror table");
+  gymfx::MirrorTable mt;
+  mt.nseg = (int)ns;
+  for (size_t s = 0; s < ns; ++s) {
+    check_bf16(mirrors[s], "mirror");
+    TORCH_CHECK(mirrors[s].dim() == 2 && mirrors[s].device() == p.device(),
+                "mirror must be [N,K] on the parameter device");
+    const int64_t N = mirrors[s].size(0), K = mirrors[s].size(1);
+    TORCH_CHECK(K * N > 0 && K * N < (1ll << 31), "mirror size");
+    TORCH_CHECK(mirror_offs[s] >= 0 && mirror_offs[s] + K * N <= n,
+                "mirror segment outside params");
+    mt.seg[s].off = mirror_offs[s];
+    mt.seg[s].K = (int)K;
+    mt.seg[s].N = (int)N;
+    mt.seg[s].dst = mirrors[s].data_ptr();
+  }
+  const float* part = nullptr;
+  int nparts = 0;
+  if (clip_part.has_value() && clip_max_norm > 0) {
+    check_f32(*clip_part, "clip_part");
+    nparts = (int)clip_part->numel();
+    if (!sumsq_done)
+      gymfx::launch_grad_sumsq(g.data_ptr<float>(), n,
+                               clip_part->data_ptr<float>(), nparts,
+                               cur_stream());
+    part = clip_part->data_ptr<float>();
+  }
+  gymfx::launch_adam_tail(p.data_ptr<float>(), g.data_ptr<float>(),
+                          m.data_ptr<float>(), v.data_ptr<float>(), pb, n,
+                          (float)lr, (float)beta1, (float)beta2, (float)eps,
+                          step_ctr.data_ptr<int>(), ticket_ptr(ticket), part,
+                          nparts, (float)clip_max_norm, mt, cur_stream());
 }
 
 void grad_clip_op(torch::Tensor g, double max_norm, torch::Tensor part,
@@ -970,7 +1095,8 @@ void mb_gather_op(torch::Tensor obs_src, torch::Tensor act_src,
                   torch::Tensor act_mb, torch::Tensor logp_mb,
                   torch::Tensor adv_mb, torch::Tensor ret_mb, int64_t seed,
                   int64_t minibatches, torch::Tensor step_base,
-                  torch::Tensor mb_ctr, bool skip_obs) {
+                  torch::Tensor mb_ctr, bool skip_obs,
+                  c10::optional<torch::Tensor> ticket) {
   check_bf16(obs_src, "obs_src");
   check_bf16(obs_mb, "obs_mb");
   const int64_t n = obs_src.size(0);
@@ -995,8 +1121,8 @@ void mb_gather_op(torch::Tensor obs_src, torch::Tensor act_src,
       adv_mb.data_ptr<float>(), ret_mb.data_ptr<float>(), M, D, (uint32_t)n,
       bits / 2, (uint64_t)seed, (int)minibatches,
       reinterpret_cast<const unsigned long long*>(step_base.data_ptr()),
-      reinterpret_cast<const unsigned long long*>(mb_ctr.data_ptr()),
-      cur_stream(), skip_obs ? 1 : 0);
+      reinterpret_cast<unsigned long long*>(mb_ctr.data_ptr()),
+      cur_stream(), skip_obs ? 1 : 0, ticket_ptr(ticket));
 }
 
 void ppo_loss_bwd_op(torch::Tensor head, torch::Tensor actions,
@@ -1088,18 +1214,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("adv_mb"), py::arg("ret_mb"), py::arg("done_mb"),
         py::arg("h0_mb"),
         py::arg("c0_mb"), py::arg("L"), py::arg("N"), py::arg("seed"),
-        py::arg("minibatches"), py::arg("step_base"), py::arg("mb_ctr"));
+        py::arg("minibatches"), py::arg("step_base"), py::arg("mb_ctr"),
+        py::arg("ticket") = py::none());
   m.def("wgrad", &wgrad_op, py::arg("X"), py::arg("dY"), py::arg("dW_part"),
         py::arg("db_part"), py::arg("dW"), py::arg("db"), py::arg("slabs"),
         py::arg("ap_seed") = 0, py::arg("ap_minibatches") = 1,
         py::arg("ap_ctr_off") = 0, py::arg("ap_step_base") = py::none(),
-        py::arg("ap_mb_ctr") = py::none());
+        py::arg("ap_mb_ctr") = py::none(), py::arg("reduce") = true);
+  m.def("grads_finalize", &grads_finalize_op, py::arg("parts"),
+        py::arg("elems"), py::arg("slabs"), py::arg("offs"),
+        py::arg("is_bias"), py::arg("grads"),
+        py::arg("clip_part") = py::none());
   m.def("gae", &gae_op);
   m.def("adam", &adam_op, py::arg("p"), py::arg("g"), py::arg("m"),
         py::arg("v"), py::arg("p_bf16"), py::arg("lr"), py::arg("beta1"),
         py::arg("beta2"), py::arg("eps"), py::arg("step"),
         py::arg("gscale") = py::none(), py::arg("step_ctr") = py::none(),
         py::arg("clip_part") = py::none(), py::arg("clip_max_norm") = 0.0);
+  m.def("adam_tail", &adam_tail_op, py::arg("p"), py::arg("g"), py::arg("m"),
+        py::arg("v"), py::arg("p_bf16"), py::arg("lr"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("step_ctr"),
+        py::arg("ticket") = py::none(), py::arg("clip_part") = py::none(),
+        py::arg("clip_max_norm") = 0.0, py::arg("sumsq_done") = false,
+        py::arg("mirror_offs") = std::vector<int64_t>(),
+        py::arg("mirrors") = std::vector<torch::Tensor>());
   m.def("grad_clip", &grad_clip_op);
   m.def("sample_head", &sample_head_op, py::arg("head"), py::arg("seed"),
         py::arg("step"), py::arg("actions"), py::arg("logp"),
@@ -1118,7 +1256,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("logp_src"), py::arg("adv_src"), py::arg("ret_src"),
         py::arg("obs_mb"), py::arg("act_mb"), py::arg("logp_mb"),
         py::arg("adv_mb"), py::arg("ret_mb"), py::arg("seed"),
-        py::arg("minibatches"), py::arg("step_base"), py::arg("mb_ctr"), py::arg("skip_obs") = false);
+        py::arg("minibatches"), py::arg("step_base"), py::arg("mb_ctr"),
+        py::arg("skip_obs") = false, py::arg("ticket") = py::none());
   m.def("ppo_loss_bwd", &ppo_loss_bwd_op, py::arg("head"), py::arg("actions"),
         py::arg("old_logp"), py::arg("adv"), py::arg("ret"), py::arg("dhead"),
         py::arg("clip_eps"), py::arg("ent_coef"), py::arg("vf_coef"),

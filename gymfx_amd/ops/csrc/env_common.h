@@ -133,6 +133,34 @@ struct FeistelMap {
   const unsigned long long* mb_ctr = nullptr;
 };
 
+// Fused optimizer tail (grads_finalize_kernel / adam_tail_kernel): small
+// by-value tables passed as kernel arguments.
+// One wgrad slab workspace to be reduced into the flat gradient buffer.
+constexpr int kMaxFinalizeSegs = 12;
+struct FinalizeSeg {
+  const float* part = nullptr;  // [slabs, elems] split-M partials
+  long long elems = 0;
+  long long off = 0;            // offset into the flat grads buffer
+  int slabs = 0;
+  int small = 0;                // 1: slab_reduce_small_kernel association
+};
+struct FinalizeTable {
+  FinalizeSeg seg[kMaxFinalizeSegs];
+  int nseg = 0;
+};
+
+// One [K,N] weight inside the flat parameter buffer and its [N,K] mirror.
+constexpr int kMaxMirrorSegs = 8;
+struct MirrorSeg {
+  long long off = 0;
+  int K = 0, N = 0;
+  void* dst = nullptr;          // bf16 [N,K]
+};
+struct MirrorTable {
+  MirrorSeg seg[kMaxMirrorSegs];
+  int nseg = 0;
+};
+
 struct EnvParamsK {
   int n_envs, T, window, n_features;
   int reward_id, strategy_id, prep_id;

@@ -852,6 +852,241 @@ __global__ void clip_scale_kernel(const float* __restrict__ part, int nparts,
 }
 
 // ---------------------------------------------------------------------------
+// Fused optimizer tail.
+//
+// Last-block ticket: folds a "+delta" counter advance into the kernel that
+// reads the counter.  Every thread of every block has loaded the counter
+// (the value is in its register) and passed a workgroup barrier before
+// thread 0 draws its ticket, so the block that draws gridDim-1 knows every
+// reader is done; it stores the new value and rearms the ticket (graph
+// replays start from 0 again).  The draw is a relaxed agent-scope atomic
+// with NO __threadfence(): nothing this launch wrote has to be visible to
+// the other blocks, only the order "all loads returned -> store" matters,
+// and the fence (an L2 write-back plus an L1 invalidate per block) measured
+// 15.4 us for the 522-block Adam launch against 5.5 us without a ticket.
+// Draw early, commit late: the atomic's round trip overlaps the block's
+// own work.
+// ---------------------------------------------------------------------------
+GFX_DEV unsigned int ticket_draw(unsigned int* ticket) {
+  return __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED,
+                                __HIP_MEMORY_SCOPE_AGENT);
+}
+
+template <typename T>
+GFX_DEV void ticket_commit(unsigned int drawn, T* ctr, T old, T delta,
+                           unsigned int* ticket) {
+  if (drawn == gridDim.x - 1u) {
+    *ctr = old + delta;
+    *ticket = 0u;
+  }
+}
+
+// grads_finalize_kernel: every wgrad slab workspace of one backward pass
+// reduced into the flat gradient buffer in ONE launch, bit-for-bit in the
+// association order of slab_reduce_kernel / slab_reduce_small_kernel, plus
+// (optionally) the 256 sum-of-squares partials sumsq_partial_kernel would
+// write for the same buffer.
+//
+// Layout: 256 blocks x 1024 threads.  Thread (q = tid>>8, t = tid&255) of
+// block b works on elements i = b*256 + t + j*65536 — exactly the elements
+// sumsq_partial_kernel's block b / thread t squares, in the same j order —
+// and the four q-threads of an element split its slab sum:
+//   vector path (elems > 4096, e < elems&~3): q sums slabs k = q, q+4, ...
+//     (the s0..s3 interleave), q = 0 adds the slabs%4 remainder, combined
+//     as (s0+s1)+(s2+s3);
+//   scalar tail (e >= elems&~3): q = 0 sums serially over k;
+//   small path: the 256 leaves of the halving tree are the serial sums over
+//     k = t', t'+256, ...; q reduces leaves t' = q+4m through tree widths
+//     128..4 in registers (m-space widths 32..1), the widths 2 and 1 are
+//     (v0+v2)+(v1+v3).
+// Each thread streams its slab column with up to 32 independent loads in
+// flight (the kernel is latency-bound below that: 16 waves per CU, one
+// block per CU).
+__global__ __launch_bounds__(1024) void grads_finalize_kernel(
+    FinalizeTable tab, float* __restrict__ grads, int64_t n,
+    float* __restrict__ clip_part) {
+  __shared__ float comb[4][256];
+  const int t = threadIdx.x & 255;
+  const int q = threadIdx.x >> 8;
+  float sq = 0.f;
+  for (int64_t base = (int64_t)blockIdx.x * 256; base < n;
+       base += (int64_t)gridDim.x * 256) {
+    const int64_t i = base + t;
+    const float* part = nullptr;
+    int64_t elems = 0, e = 0;
+    int slabs = 0, small = 0;
+#pragma unroll
+    for (int s = 0; s < kMaxFinalizeSegs; ++s) {
+      const int64_t d = i - tab.seg[s].off;
+      if (s < tab.nseg && i < n && d >= 0 && d < tab.seg[s].elems) {
+        part = tab.seg[s].part;
+        elems = tab.seg[s].elems;
+        e = d;
+        slabs = tab.seg[s].slabs;
+        small = tab.seg[s].small;
+      }
+    }
+    int kind = -1;  // 0 vector path, 1 scalar tail, 2 small tree
+    float val = 0.f;
+    if (part) {
+      const float* pe = part + e;
+      if (small) {
+        kind = 2;
+        // leaf m = serial sum over k = q+4m, +256, ...; a slab past the
+        // end adds +0.f, which leaves the sum's bits alone (its load is
+        // clamped in bounds and discarded).  16 loads in flight per round.
+        float r[64];
+#pragma unroll
+        for (int m = 0; m < 64; ++m) r[m] = 0.f;
+#pragma unroll
+        for (int h = 0; h < 64; h += 16) {
+          for (int k0 = q + 4 * h; k0 < slabs; k0 += 256) {
+            float x[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u)
+              x[u] = pe[(int64_t)min(k0 + 4 * u, slabs - 1) * elems];
+#pragma unroll
+            for (int u = 0; u < 16; ++u)
+              r[h + u] += (k0 + 4 * u < slabs) ? x[u] : 0.f;
+          }
+        }
+#pragma unroll
+        for (int w = 32; w > 0; w >>= 1)
+#pragma unroll
+          for (int m = 0; m < w; ++m) r[m] += r[m + w];
+        val = r[0];
+      } else if (e < (elems & ~(int64_t)3)) {
+        kind = 0;
+        const int kend = slabs & ~3;
+        float s = 0.f;
+        int k = q;
+        for (; k + 124 < kend; k += 128) {
+          float x[32];
+#pragma unroll
+          for (int u = 0; u < 32; ++u) x[u] = pe[(int64_t)(k + 4 * u) * elems];
+#pragma unroll
+          for (int u = 0; u < 32; ++u) s += x[u];
+        }
+        for (; k + 60 < kend; k += 64) {
+          float x[16];
+#pragma unroll
+          for (int u = 0; u < 16; ++u) x[u] = pe[(int64_t)(k + 4 * u) * elems];
+#pragma unroll
+          for (int u = 0; u < 16; ++u) s += x[u];
+        }
+        for (; k < kend; k += 4) s += pe[(int64_t)k * elems];
+        if (q == 0)
+          for (k = kend; k < slabs; ++k) s += pe[(int64_t)k * elems];
+        val = s;
+      } else {
+        kind = 1;
+        if (q == 0) {
+          float s = 0.f;
+          for (int k = 0; k < slabs; ++k) s += pe[(int64_t)k * elems];
+          val = s;
+        }
+      }
+    }
+    comb[q][t] = val;
+    __syncthreads();
+    if (q == 0 && i < n) {
+      float g;
+      if (kind == 0)
+        g = (comb[0][t] + comb[1][t]) + (comb[2][t] + comb[3][t]);
+      else if (kind == 2)
+        g = (comb[0][t] + comb[2][t]) + (comb[1][t] + comb[3][t]);
+      else if (kind == 1)
+        g = val;
+      else
+        g = grads[i];  // not covered by any segment: left as it is
+      if (kind >= 0) grads[i] = g;
+      sq += g * g;
+    }
+    __syncthreads();
+  }
+  if (clip_part) {
+    // block b's partial: same per-thread serial sums, same halving tree
+    __shared__ float red[256];
+    if (q == 0) red[t] = sq;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (q == 0 && t < w) red[t] += red[t + w];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) clip_part[blockIdx.x] = red[0];
+  }
+}
+
+// adam_tail_kernel: adam_kernel with the two launches that followed it
+// folded in.  (1) For an element inside a [K,N] weight segment the bf16
+// value written to p_bf16[i] is stored a second time at mirror[n*K + k],
+// which is what transpose_bf16_kernel produced from p_bf16 (the whole model
+// is a few hundred KB, so the scattered 2-byte stores stay in L2).  (2) The
+// step counter is advanced by the last-block ticket instead of the
+// increment kernel.  The per-element update is adam_kernel's, expression
+// for expression.
+__global__ __launch_bounds__(1024) void adam_tail_kernel(
+    float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+    float* __restrict__ v, __bf16* __restrict__ p_bf16, int64_t n, float lr,
+    float beta1, float beta2, float eps, int* step_ctr,
+    unsigned int* ticket, const float* __restrict__ clip_part, int nparts,
+    float max_norm, MirrorTable mt) {
+  // 1024-thread blocks (adam_kernel: 256): a quarter of the tickets to
+  // draw; the per-element update does not depend on the launch geometry.
+  const int ctr = *(volatile const int*)step_ctr;
+  __syncthreads();
+  unsigned int drawn = 0;
+  const bool drawer = ticket && threadIdx.x == 0;
+  if (drawer) drawn = ticket_draw(ticket);
+  const float st = (float)(ctr + 1);
+  const float bc1 = 1.f - powf(beta1, st);
+  const float bc2 = 1.f - powf(beta2, st);
+  float s = 1.f;
+  if (clip_part) {
+    // adam_kernel's 256-thread tree, run by the first 256 threads
+    __shared__ float red[256];
+    if (threadIdx.x < 256) {
+      float acc = 0.f;
+      for (int i = threadIdx.x; i < nparts; i += 256) acc += clip_part[i];
+      red[threadIdx.x] = acc;
+    }
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+      if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+      __syncthreads();
+    }
+    const float norm = sqrtf(red[0]);
+    s = (max_norm > 0.f && norm > max_norm) ? max_norm / norm : 1.f;
+  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const float gi = g[i] * s;
+    const float mi = beta1 * m[i] + (1.f - beta1) * gi;
+    const float vi = beta2 * v[i] + (1.f - beta2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    const float mhat = mi / bc1;
+    const float vhat = vi / bc2;
+    const float pi = p[i] - lr * mhat / (sqrtf(vhat) + eps);
+    p[i] = pi;
+    const __bf16 pb = f2bf(pi);
+    if (p_bf16) p_bf16[i] = pb;
+#pragma unroll
+    for (int sgi = 0; sgi < kMaxMirrorSegs; ++sgi) {
+      const int64_t d = i - mt.seg[sgi].off;
+      if (sgi < mt.nseg && d >= 0 &&
+          d < (int64_t)mt.seg[sgi].K * mt.seg[sgi].N) {
+        const unsigned K = (unsigned)mt.seg[sgi].K, N = (unsigned)mt.seg[sgi].N;
+        const unsigned k = (unsigned)d / N;
+        const unsigned c = (unsigned)d - k * N;
+        reinterpret_cast<__bf16*>(mt.seg[sgi].dst)[(int64_t)c * K + k] = pb;
+      }
+    }
+  }
+  if (drawer) ticket_commit(drawn, step_ctr, ctr, 1, ticket);
+}
+
+// ---------------------------------------------------------------------------
 // Categorical sampling + logp + entropy from the fused head output
 // head[M, A+1] f32: cols 0..A-1 logits, col A value.
 // Counter-based RNG (splitmix64): deterministic in (seed, step, env).
@@ -1745,6 +1980,10 @@ __global__ void increment_i32_kernel(int* __restrict__ ctr, int delta) {
 // mb_ctr (device) = epoch * minibatches + mb, advanced by increment after
 // the gather inside the captured graph; step_base keys the epoch permutation
 // to the rollout counter so every update reshuffles.
+// TICKET: this launch also advances mb_ctr (no increment kernel follows) —
+// see ticket_draw.  TICKET = false is the kernel as it always was: the
+// counter stays on the scalar path and so does the whole key schedule.
+template <bool TICKET>
 __global__ __launch_bounds__(256) void mb_gather_kernel(
     const __bf16* __restrict__ obs_src, const int64_t* __restrict__ act_src,
     const float* __restrict__ logp_src, const float* __restrict__ adv_src,
@@ -1753,11 +1992,20 @@ __global__ __launch_bounds__(256) void mb_gather_kernel(
     float* __restrict__ adv_mb, float* __restrict__ ret_mb, int M, int D,
     uint32_t n, int half, uint64_t seed, int minibatches,
     const unsigned long long* __restrict__ step_base,
-    const unsigned long long* __restrict__ mb_ctr, int skip_obs) {
+    unsigned long long* mb_ctr, int skip_obs, unsigned int* ticket) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  if (row >= M) return;
-  const unsigned long long ctr = *mb_ctr;
+  unsigned long long ctr;
+  if (TICKET) {
+    ctr = *(volatile const unsigned long long*)mb_ctr;
+    __syncthreads();
+    if (threadIdx.x == 0)
+      ticket_commit(ticket_draw(ticket), mb_ctr, ctr, 1ull, ticket);
+    if (row >= M) return;
+  } else {
+    if (row >= M) return;
+    ctr = *mb_ctr;
+  }
   const uint32_t epoch = (uint32_t)(ctr / (unsigned)minibatches);
   const uint32_t mb = (uint32_t)(ctr % (unsigned)minibatches);
   const uint64_t key = splitmix64(seed ^ (*step_base * 0x9E3779B97F4A7C15ull) ^
@@ -1794,6 +2042,7 @@ __global__ __launch_bounds__(256) void mb_gather_kernel(
 // so the minibatch tensors are [L, Mseq, ...] (time-major for the BPTT
 // loop).  h0/c0 are the saved chunk-boundary recurrent states.
 // ---------------------------------------------------------------------------
+template <bool TICKET>
 __global__ __launch_bounds__(256) void mb_gather_seq_kernel(
     const __bf16* __restrict__ obs_src,   // [T, N, D] flat
     const int64_t* __restrict__ act_src,  // [T, N]
@@ -1812,11 +2061,20 @@ __global__ __launch_bounds__(256) void mb_gather_seq_kernel(
     int Mseq, int L, int D, int H, int N, uint32_t n_seq, int half,
     uint64_t seed, int minibatches,
     const unsigned long long* __restrict__ step_base,
-    const unsigned long long* __restrict__ mb_ctr) {
+    unsigned long long* mb_ctr, unsigned int* ticket) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);  // seq within mb
   const int lane = threadIdx.x & 63;
-  if (row >= Mseq) return;
-  const unsigned long long ctr = *mb_ctr;
+  unsigned long long ctr;
+  if (TICKET) {
+    ctr = *(volatile const unsigned long long*)mb_ctr;
+    __syncthreads();
+    if (threadIdx.x == 0)
+      ticket_commit(ticket_draw(ticket), mb_ctr, ctr, 1ull, ticket);
+    if (row >= Mseq) return;
+  } else {
+    if (row >= Mseq) return;
+    ctr = *mb_ctr;
+  }
   const uint32_t epoch = (uint32_t)(ctr / (unsigned)minibatches);
   const uint32_t mb = (uint32_t)(ctr % (unsigned)minibatches);
   const uint64_t key = splitmix64(seed ^ (*step_base * 0x9E3779B97F4A7C15ull) ^
@@ -1968,16 +2226,21 @@ void launch_mb_gather_seq(const void* obs_src, const int64_t* act_src,
                           int H, int N, uint32_t n_seq, int half,
                           uint64_t seed, int minibatches,
                           const unsigned long long* step_base,
-                          const unsigned long long* mb_ctr,
+                          unsigned long long* mb_ctr, unsigned int* ticket,
                           hipStream_t stream) {
-  hipLaunchKernelGGL(mb_gather_seq_kernel, dim3(ceil_div(Mseq, 4)), dim3(256),
-                     0, stream, reinterpret_cast<const __bf16*>(obs_src),
-                     act_src, logp_src, adv_src, ret_src, done_src, h0_src,
-                     c0_src, reinterpret_cast<__bf16*>(obs_mb), act_mb,
-                     logp_mb, adv_mb, ret_mb, done_mb,
-                     reinterpret_cast<__bf16*>(h0_mb), c0_mb,
-                     Mseq, L, D, H, N, n_seq, half, seed, minibatches,
-                     step_base, mb_ctr);
+#define GATHER_SEQ(TK)                                                        \
+  hipLaunchKernelGGL(mb_gather_seq_kernel<TK>, dim3(ceil_div(Mseq, 4)),       \
+                     dim3(256), 0, stream,                                    \
+                     reinterpret_cast<const __bf16*>(obs_src), act_src,       \
+                     logp_src, adv_src, ret_src, done_src, h0_src, c0_src,    \
+                     reinterpret_cast<__bf16*>(obs_mb), act_mb, logp_mb,      \
+                     adv_mb, ret_mb, done_mb,                                 \
+                     reinterpret_cast<__bf16*>(h0_mb), c0_mb, Mseq, L, D, H,  \
+                     N, n_seq, half, seed, minibatches, step_base, mb_ctr,    \
+                     ticket)
+  if (ticket) GATHER_SEQ(true);
+  else GATHER_SEQ(false);
+#undef GATHER_SEQ
 }
 
 void launch_mlp_policy_rollout(const void* obs, const void* W1t,
@@ -2016,14 +2279,18 @@ void launch_mb_gather(const void* obs_src, const int64_t* act_src,
                       float* logp_mb, float* adv_mb, float* ret_mb, int M,
                       int D, uint32_t n, int half, uint64_t seed,
                       int minibatches, const unsigned long long* step_base,
-                      const unsigned long long* mb_ctr, hipStream_t stream,
-                      int skip_obs) {
-  hipLaunchKernelGGL(mb_gather_kernel, dim3(ceil_div(M, 4)), dim3(256), 0,
-                     stream, reinterpret_cast<const __bf16*>(obs_src), act_src,
-                     logp_src, adv_src, ret_src,
-                     reinterpret_cast<__bf16*>(obs_mb), act_mb, logp_mb, adv_mb,
-                     ret_mb, M, D, n, half, seed, minibatches, step_base,
-                     mb_ctr, skip_obs);
+                      unsigned long long* mb_ctr, hipStream_t stream,
+                      int skip_obs, unsigned int* ticket) {
+#define GATHER(TK)                                                            \
+  hipLaunchKernelGGL(mb_gather_kernel<TK>, dim3(ceil_div(M, 4)), dim3(256),   \
+                     0, stream, reinterpret_cast<const __bf16*>(obs_src),     \
+                     act_src, logp_src, adv_src, ret_src,                     \
+                     reinterpret_cast<__bf16*>(obs_mb), act_mb, logp_mb,      \
+                     adv_mb, ret_mb, M, D, n, half, seed, minibatches,        \
+                     step_base, mb_ctr, skip_obs, ticket)
+  if (ticket) GATHER(true);
+  else GATHER(false);
+#undef GATHER
 }
 
 void launch_gemm(const void* A, const void* B, const float* bias, void* C,
@@ -2140,7 +2407,8 @@ void launch_gemm(const void* A, const void* B, const float* bias, void* C,
 
 void launch_wgrad(const void* X, const void* dY, float* dW_part, float* db_part,
                   float* dW, float* db, int M, int N, int K, int slabs,
-                  hipStream_t stream, const FeistelMap* fmp = nullptr) {
+                  hipStream_t stream, const FeistelMap* fmp = nullptr,
+                  bool reduce = true) {
   const __bf16* x = reinterpret_cast<const __bf16*>(X);
   const __bf16* dy = reinterpret_cast<const __bf16*>(dY);
   // Tile choice: 128x128 halves the HBM re-streaming of X/dY — wgrad runs
@@ -2222,6 +2490,9 @@ void launch_wgrad(const void* X, const void* dY, float* dW_part, float* db_part,
     }
 #undef WG_PART
   }
+  // reduce == false: the partials stay in dW_part/db_part and
+  // launch_grads_finalize reduces every layer's workspace in one launch
+  if (!reduce) return;
   int64_t elems = (int64_t)K * N;
   if (elems <= 4096) {
     hipLaunchKernelGGL(slab_reduce_small_kernel, dim3((int)elems), dim3(256),
@@ -2277,6 +2548,29 @@ void launch_grad_sumsq(const float* g, int64_t n, float* part, int nparts,
                        hipStream_t stream) {
   hipLaunchKernelGGL(sumsq_partial_kernel, dim3(nparts), dim3(256), 0, stream,
                      g, n, part);
+}
+
+void launch_grads_finalize(const FinalizeTable& tab, float* grads, int64_t n,
+                           float* clip_part, hipStream_t stream) {
+  // with norm partials the grid IS the 256-partial layout of
+  // sumsq_partial_kernel; without, no more blocks than there is work
+  const int blocks =
+      clip_part ? 256 : (int)std::min<int64_t>((n + 255) / 256, 256);
+  hipLaunchKernelGGL(grads_finalize_kernel, dim3(blocks), dim3(1024), 0,
+                     stream, tab, grads, n, clip_part);
+}
+
+void launch_adam_tail(float* p, const float* g, float* m, float* v,
+                      void* p_bf16, int64_t n, float lr, float beta1,
+                      float beta2, float eps, int* step_ctr,
+                      unsigned int* ticket, const float* clip_part, int nparts,
+                      float max_norm, const MirrorTable& mt,
+                      hipStream_t stream) {
+  int blocks = (int)std::min<int64_t>((n + 1023) / 1024, 2048);
+  hipLaunchKernelGGL(adam_tail_kernel, dim3(blocks), dim3(1024), 0, stream, p,
+                     g, m, v, reinterpret_cast<__bf16*>(p_bf16), n, lr, beta1,
+                     beta2, eps, step_ctr, ticket, clip_part, nparts, max_norm,
+                     mt);
 }
 
 void launch_sample_head(const float* head, int M, int n_actions, uint64_t seed,
