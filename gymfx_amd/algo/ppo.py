@@ -82,6 +82,13 @@ class PPOConfig:
                                  # (tests/test_gpu_opt_tail.py); +2.7 % on
                                  # the MLP headline.  MLP only: measured
                                  # slower on the LSTM (PERF_NOTES.md).
+    fused_head_bwd: bool = True  # head GEMM + PPO loss backward + W3 wgrad
+                                 # + head dgrad of every minibatch step in
+                                 # ONE kernel that reads h2 once (hidden 256,
+                                 # head_dim <= 16, <= 128 rows per W3 wgrad
+                                 # slab; other shapes keep the four launches).
+                                 # Bitwise == the four-launch sequence
+                                 # (tests/test_gpu_head_bwd.py).  MLP only.
 
     @classmethod
     def from_config(cls, cfg: Dict[str, Any]) -> "PPOConfig":
@@ -109,6 +116,7 @@ class PPOConfig:
             "fuse_head": "fuse_head",
             "overlap_gather": "overlap_gather",
             "fused_opt_tail": "fused_opt_tail",
+            "fused_head_bwd": "fused_head_bwd",
         }
         from ..config.merger import convert_type
 
@@ -278,6 +286,15 @@ class PPOTrainer:
         self.model.fused_tail = self._fused_tail
         self.model.fuse_norm = (self._fused_tail and world_size <= 1
                                 and cfg.max_grad_norm > 0)
+        # fused head forward / loss / head backward (api.head_loss_bwd):
+        # the feed-forward trainer's materialized-minibatch paths (the
+        # _fuse_gather branch of _fwd_bwd_body keeps its own sequence)
+        self._fused_head = bool(cfg.fused_head_bwd) and not self.recurrent
+        # its logging sums go to 64 accumulator rows on separate cache lines
+        # (api.head_loss_bwd) and update() folds them into self.losses once
+        self._loss_shards = (
+            torch.zeros(64, 32, dtype=torch.float32, device=dev)
+            if self._fused_head and self.device.type == "cuda" else None)
         # ticket word of the in-kernel mb_ctr advance (ops/api.mb_gather).
         # MEASURED NEGATIVE at the flagship shape: the gather launches one
         # block per 4 rows (16384 blocks), and 16384 draws on one word took
@@ -480,6 +497,18 @@ class PPOTrainer:
             model.bptt_backward(self.obs_mb_seq, self.done_mb, self.dhead,
                                 self.bptt)
             return
+        if self._fused_head and not self._fuse_gather:
+            model.forward_hidden(self.obs_mb_s[slot], self.acts_train)
+            model.head_loss_backward(
+                self.acts_train, self.act_mb_s[slot], self.logp_mb_s[slot],
+                self.adv_mb_s[slot], self.ret_mb_s[slot], self.dhead,
+                self.scratch, clip_eps=cfg.clip_eps, ent_coef=cfg.ent_coef,
+                vf_coef=cfg.vf_coef, inv_count=1.0 / self.mb_rows,
+                losses=self._loss_acc(),
+            )
+            model.backward(self.obs_mb_s[slot], self.acts_train, self.dhead,
+                           self.scratch, skip_head=True)
+            return
         if self._fuse_gather:
             # obs rows come straight from the rollout slab through the
             # permutation (mb_ctr was already advanced by the gather of the
@@ -502,6 +531,15 @@ class PPOTrainer:
             model.backward(self.obs_mb_s[slot], self.acts_train, self.dhead,
                            self.scratch)
 
+    def _loss_acc(self) -> torch.Tensor:
+        """Where the fused head kernel accumulates its logging sums."""
+        return self.losses if self._loss_shards is None else self._loss_shards
+
+    def _fold_losses(self) -> None:
+        """End of update(): the sharded logging sums into self.losses."""
+        if self._loss_shards is not None:
+            self.losses.add_(self._loss_shards[:, :5].sum(dim=0))
+
     def _mb_body(self, slot: int = 0) -> None:
         self._gather_body(slot)
         self._fwd_bwd_body(slot)
@@ -516,6 +554,17 @@ class PPOTrainer:
         self.logp_mb.copy_(self.logp_flat[sl])
         self.adv_mb.copy_(self.adv_flat[sl])
         self.ret_mb.copy_(self.ret_flat[sl])
+        if self._fused_head:
+            model.forward_hidden(self.obs_mb, self.acts_train)
+            model.head_loss_backward(
+                self.acts_train, self.act_mb, self.logp_mb, self.adv_mb,
+                self.ret_mb, self.dhead, self.scratch, clip_eps=cfg.clip_eps,
+                ent_coef=cfg.ent_coef, vf_coef=cfg.vf_coef, inv_count=1.0 / M,
+                losses=self._loss_acc(),
+            )
+            model.backward(self.obs_mb, self.acts_train, self.dhead,
+                           self.scratch, skip_head=True)
+            return
         head = model.forward(self.obs_mb, self.acts_train)
         api.ppo_loss_bwd(
             head, self.act_mb, self.logp_mb, self.adv_mb, self.ret_mb,
@@ -620,6 +669,8 @@ class PPOTrainer:
     def update(self, with_stats: bool = True) -> Dict[str, float]:
         cfg = self.cfg
         self.losses.zero_()
+        if self._loss_shards is not None:
+            self._loss_shards.zero_()
         self.mb_ctr.zero_()
         graphs = self.use_graphs and self._graphs_ready
         n_mb = cfg.ppo_epochs * cfg.minibatches
@@ -628,6 +679,7 @@ class PPOTrainer:
                 self._mb_body_noshuffle(i)
                 self._allreduce_grads()
                 self._opt_body()
+            self._fold_losses()
             self.update_count += 1
             return self._stats(n_mb) if with_stats else {}
         def gather(slot: int) -> None:
@@ -659,6 +711,7 @@ class PPOTrainer:
                     gather(0)
                 self._reducer.finish()
                 opt()
+            self._fold_losses()
             self.update_count += 1
             return self._stats(n_mb) if with_stats else {}
         # two-stream pipeline (ping-pong minibatch slots): gather(i+1) is
@@ -687,6 +740,7 @@ class PPOTrainer:
             opt()
             if i + 1 < n_mb:
                 main.wait_event(ev_g[nxt])
+        self._fold_losses()
         self.update_count += 1
         return self._stats(n_mb) if with_stats else {}
 

@@ -92,6 +92,7 @@ DEFAULT_VALUES = {
     "fuse_sample": True,         # sample inside the env-step kernel (GPU)
     "overlap_gather": False,     # side-stream mb gather (measured slower)
     "fused_opt_tail": True,      # 2-launch reduce/optimizer tail per minibatch
+    "fused_head_bwd": True,      # head fwd + loss bwd + head bwd in one kernel
     "checkpoint_file": None,     # save/resume path (mode=training)
     "checkpoint_interval": 0,    # save every N updates (0 = final only)
     "resume": False,

@@ -197,10 +197,41 @@ class ActorCriticMLP:
                        acts: Dict[str, torch.Tensor]) -> torch.Tensor:
         """Layers 1-2 only: the rollout's head-in-step fusion computes the
         tiny head GEMM inside the env kernel (h2 @ W3 + b3 per env row),
-        removing one launch from the latency-bound per-step chain."""
+        removing one launch from the latency-bound per-step chain; in the
+        update, head_loss_backward computes the head from h2 itself."""
         api.gemm(obs_bf16, self.wt("W1"), self.f32("b1"), acts["h1"], act=2, trans_b=True)
         api.gemm(acts["h1"], self.wt("W2"), self.f32("b2"), acts["h2"], act=2, trans_b=True)
         return acts["h2"]
+
+    # -- head forward + loss backward + head-layer backward ---------------
+    def head_loss_backward(
+        self,
+        acts: Dict[str, torch.Tensor],
+        actions: torch.Tensor,
+        old_logp: torch.Tensor,
+        adv: torch.Tensor,
+        ret: torch.Tensor,
+        dhead: torch.Tensor,
+        scratch: Dict[str, torch.Tensor],
+        *,
+        clip_eps: float,
+        ent_coef: float,
+        vf_coef: float,
+        inv_count: float,
+        losses: Optional[torch.Tensor] = None,
+    ) -> None:
+        """After forward_hidden: acts["head"], dhead, the W3/b3 gradient
+        (slab partials; reduced here unless the fused tail does it) and
+        scratch["dh2"] in one api.head_loss_bwd call.  Follow with
+        backward(..., skip_head=True)."""
+        dw_p, db_p, slabs = self._wg_workspace("W3", self.hidden, self.head_dim, True)
+        api.head_loss_bwd(
+            acts["h2"], self.wt("W3"), self.w("W3"), self.f32("b3"), actions,
+            old_logp, adv, ret, acts["head"], dhead, scratch["dh2"],
+            self.grad("W3"), self.grad("b3"), workspace=(dw_p, db_p),
+            slabs=slabs, reduce=not self.fused_tail, clip_eps=clip_eps,
+            ent_coef=ent_coef, vf_coef=vf_coef, inv_count=inv_count,
+            losses=losses)
 
     # -- backward (dhead [M, A+1] bf16 -> accumulate grads) --------------
     def backward(
@@ -210,7 +241,10 @@ class ActorCriticMLP:
         dhead: torch.Tensor,
         scratch: Dict[str, torch.Tensor],
         a_feistel: "Optional[dict]" = None,
+        skip_head: bool = False,
     ) -> None:
+        """skip_head: start at layer 2 — head_loss_backward has already
+        issued the W3 wgrad and the head dgrad (scratch["dh2"] is set)."""
         M = dhead.shape[0]
         dh2 = scratch["dh2"]
         dh1 = scratch["dh1"]
@@ -218,11 +252,12 @@ class ActorCriticMLP:
         # grads_finalize launch at the end reduces all six slices
         red = not self.fused_tail
         # head layer
-        dw_p, db_p, slabs = self._wg_workspace("W3", self.hidden, self.head_dim, True)
-        api.wgrad(acts["h2"], dhead, self.grad("W3"), self.grad("b3"),
-                  workspace=(dw_p, db_p), slabs=slabs, reduce=red)
-        api.gemm(dhead, self.w("W3"), None, dh2, Yact=acts["h2"], trans_b=True,
-                 act=1, dact_tanh=True)
+        if not skip_head:
+            dw_p, db_p, slabs = self._wg_workspace("W3", self.hidden, self.head_dim, True)
+            api.wgrad(acts["h2"], dhead, self.grad("W3"), self.grad("b3"),
+                      workspace=(dw_p, db_p), slabs=slabs, reduce=red)
+            api.gemm(dhead, self.w("W3"), None, dh2, Yact=acts["h2"], trans_b=True,
+                     act=1, dact_tanh=True)
         # layer 2
         dw_p, db_p, slabs = self._wg_workspace("W2", self.hidden, self.hidden, True)
         api.wgrad(acts["h1"], dh2, self.grad("W2"), self.grad("b2"),

@@ -578,6 +578,79 @@ def ppo_loss_bwd(
         losses[4] += float(clipped.to(torch.float32).sum()) * inv_count
 
 
+def head_loss_bwd_fusable(M: int, hidden: int, head_dim: int,
+                          slabs: int) -> bool:
+    """Shapes head_loss_bwd_kernel takes: one block stages one wgrad slab of
+    at most 128 rows of a 256-wide h2, the head is one MFMA fragment."""
+    return (hidden == 256 and 2 <= head_dim <= 16 and slabs >= 1
+            and (M + slabs - 1) // slabs <= 128)
+
+
+def head_loss_bwd(
+    h2: torch.Tensor,
+    W3t: torch.Tensor,
+    W3: torch.Tensor,
+    b3: torch.Tensor,
+    actions: torch.Tensor,
+    old_logp: torch.Tensor,
+    adv: torch.Tensor,
+    ret: torch.Tensor,
+    head: torch.Tensor,
+    dhead: torch.Tensor,
+    dh2: torch.Tensor,
+    dW: torch.Tensor,
+    db: torch.Tensor,
+    *,
+    workspace: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+    slabs: int = 64,
+    reduce: bool = True,
+    clip_eps: float,
+    ent_coef: float,
+    vf_coef: float,
+    inv_count: float,
+    losses: Optional[torch.Tensor] = None,
+) -> None:
+    """The head layer of the MLP update in one call: head = h2 @ W3 + b3
+    (f32), dhead = PPO loss backward (bf16), the W3/b3 wgrad (slab partials
+    into ``workspace``; reduced into dW/db unless ``reduce=False``) and
+    dh2 = dhead @ W3^T * (1 - h2^2).  W3t is the [head_dim, hidden] mirror
+    of W3 [hidden, head_dim].
+
+    On the GPU this is ONE kernel when ``head_loss_bwd_fusable`` holds, and
+    its outputs are bit for bit those of the four calls below, which every
+    other shape (and the CPU oracle) takes.  Only ``losses`` may differ in
+    the last bits (atomicAdd logging sums).
+
+    ``losses`` is the usual [5] accumulator or a sharded one, [S, 32] f32:
+    the fused kernel's block b then adds into row ``b % S`` (columns 0..4)
+    and the caller sums the rows.  512 blocks adding into one cache line is
+    what the kernel would otherwise spend most of its time on (float atomics
+    on one line retire at ~88/us); the four-launch path adds into row 0."""
+    M, hidden = h2.shape
+    head_dim = W3.shape[1]
+    if _use_native(h2) and head_loss_bwd_fusable(M, hidden, head_dim, slabs):
+        if workspace is None:
+            workspace = (
+                torch.empty(slabs, hidden, head_dim, dtype=torch.float32,
+                            device=h2.device),
+                torch.empty(slabs, head_dim, dtype=torch.float32,
+                            device=h2.device),
+            )
+        native.require().head_loss_bwd(
+            h2, W3t, W3, b3, actions, old_logp, adv, ret, head, dhead, dh2,
+            workspace[0], workspace[1], dW, db, slabs, reduce, clip_eps,
+            ent_coef, vf_coef, inv_count, losses)
+        return
+    if losses is not None and losses.dim() == 2:
+        losses = losses[0]
+    gemm(h2, W3t, b3, head, act=0, trans_b=True)
+    ppo_loss_bwd(head, actions, old_logp, adv, ret, dhead, clip_eps=clip_eps,
+                 ent_coef=ent_coef, vf_coef=vf_coef, inv_count=inv_count,
+                 losses=losses)
+    wgrad(h2, dhead, dW, db, workspace=workspace, slabs=slabs, reduce=reduce)
+    gemm(dhead, W3, None, dh2, Yact=h2, trans_b=True, act=1, dact_tanh=True)
+
+
 def adv_normalize(adv: torch.Tensor, part: torch.Tensor) -> None:
     if _use_native(adv):
         native.require().adv_normalize(adv, part)

@@ -121,6 +121,16 @@ void launch_ppo_loss_bwd(const float* head, const int64_t* actions,
                          const float* ret, void* dhead, int M, int n_actions,
                          float clip_eps, float ent_coef, float vf_coef,
                          float inv_count, float* losses, hipStream_t stream);
+void launch_head_loss_bwd(const void* h2, const void* W3t, const void* W3,
+                          const float* b3, const int64_t* actions,
+                          const float* old_logp, const float* adv,
+                          const float* ret, float* head, void* dhead,
+                          void* dh2, float* dW_part, float* db_part, int M,
+                          int head_dim, int slabs, float clip_eps,
+                          float ent_coef, float vf_coef, float inv_count,
+                          float* losses, int loss_shards, hipStream_t stream);
+void launch_slab_reduce(const float* dW_part, const float* db_part, float* dW,
+                        float* db, int N, int K, int slabs, hipStream_t stream);
 void launch_adv_normalize(float* adv, int64_t n, float* part, int nparts,
                           hipStream_t stream);
 void launch_f32_to_bf16(const float* in, void* out, int64_t n,
@@ -1142,6 +1152,86 @@ void ppo_loss_bwd_op(torch::Tensor head, torch::Tensor actions,
       losses.has_value() ? losses->data_ptr<float>() : nullptr, cur_stream());
 }
 
+// Head forward + PPO loss backward + W3/b3 wgrad partials + head dgrad in
+// one launch (head_loss_bwd_kernel), bitwise the gemm / ppo_loss_bwd /
+// wgrad / gemm(dact_tanh) sequence.  The shape limits are the kernel's: the
+// caller (ops/api.py) takes the four-launch path outside them.
+// reduce: also run wgrad's own slab reduces into dW/db.
+// losses: [5] accumulator, or [S, 32] shards (block b adds into row b % S,
+// columns 0..4; the caller sums the rows).
+void head_loss_bwd_op(torch::Tensor h2, torch::Tensor W3t, torch::Tensor W3,
+                      torch::Tensor b3, torch::Tensor actions,
+                      torch::Tensor old_logp, torch::Tensor adv,
+                      torch::Tensor ret, torch::Tensor head,
+                      torch::Tensor dhead, torch::Tensor dh2,
+                      torch::Tensor dW_part, torch::Tensor db_part,
+                      torch::Tensor dW, torch::Tensor db, int64_t slabs,
+                      bool reduce, double clip_eps, double ent_coef,
+                      double vf_coef, double inv_count,
+                      c10::optional<torch::Tensor> losses) {
+  check_bf16(h2, "h2");
+  check_bf16(W3t, "W3t");
+  check_bf16(W3, "W3");
+  check_f32(b3, "b3");
+  check_f32(head, "head");
+  check_bf16(dhead, "dhead");
+  check_bf16(dh2, "dh2");
+  check_f32(dW_part, "dW_part");
+  check_f32(db_part, "db_part");
+  check_f32(dW, "dW");
+  check_f32(db, "db");
+  check_f32(old_logp, "old_logp");
+  check_f32(adv, "adv");
+  check_f32(ret, "ret");
+  const int64_t M = h2.size(0), H = h2.size(1), hd = W3.size(1);
+  TORCH_CHECK(H == 256 && hd >= 2 && hd <= 16,
+              "head_loss_bwd: needs hidden == 256 and head_dim <= 16");
+  TORCH_CHECK(slabs >= 1 && (M + slabs - 1) / slabs <= 128,
+              "head_loss_bwd: needs ceil(M/slabs) <= 128");
+  TORCH_CHECK(W3.size(0) == H && W3t.size(0) == hd && W3t.size(1) == H &&
+                  b3.numel() == hd, "head_loss_bwd: weight shapes");
+  TORCH_CHECK(head.size(0) == M && head.size(1) == hd && dhead.size(0) == M &&
+                  dhead.size(1) == hd && dh2.size(0) == M && dh2.size(1) == H,
+              "head_loss_bwd: activation shapes");
+  TORCH_CHECK(actions.scalar_type() == torch::kInt64 && actions.numel() == M &&
+                  old_logp.numel() == M && adv.numel() == M &&
+                  ret.numel() == M, "head_loss_bwd: per-row inputs");
+  TORCH_CHECK(h2.is_contiguous() && W3.is_contiguous() &&
+                  W3t.is_contiguous() && head.is_contiguous() &&
+                  dhead.is_contiguous() && dh2.is_contiguous() &&
+                  actions.is_contiguous() && old_logp.is_contiguous() &&
+                  adv.is_contiguous() && ret.is_contiguous(),
+              "head_loss_bwd: contiguous tensors only");
+  TORCH_CHECK(dW_part.numel() >= slabs * H * hd, "dW_part too small");
+  TORCH_CHECK(db_part.numel() >= slabs * hd, "db_part too small");
+  TORCH_CHECK(dW.numel() == H * hd && db.numel() == hd, "dW/db shape");
+  int loss_shards = 1;
+  if (losses.has_value()) {
+    check_f32(*losses, "losses");
+    if (losses->dim() == 2) {
+      TORCH_CHECK(losses->size(1) == 32 && losses->size(0) >= 1,
+                  "sharded losses must be [S, 32]");
+      loss_shards = (int)losses->size(0);
+    } else {
+      TORCH_CHECK(losses->numel() >= 5, "losses numel");
+    }
+  }
+  gymfx::launch_head_loss_bwd(
+      h2.data_ptr(), W3t.data_ptr(), W3.data_ptr(), b3.data_ptr<float>(),
+      actions.data_ptr<int64_t>(), old_logp.data_ptr<float>(),
+      adv.data_ptr<float>(), ret.data_ptr<float>(), head.data_ptr<float>(),
+      dhead.data_ptr(), dh2.data_ptr(), dW_part.data_ptr<float>(),
+      db_part.data_ptr<float>(), (int)M, (int)hd, (int)slabs, (float)clip_eps,
+      (float)ent_coef, (float)vf_coef, (float)inv_count,
+      losses.has_value() ? losses->data_ptr<float>() : nullptr, loss_shards,
+      cur_stream());
+  if (reduce)
+    gymfx::launch_slab_reduce(dW_part.data_ptr<float>(),
+                              db_part.data_ptr<float>(), dW.data_ptr<float>(),
+                              db.data_ptr<float>(), (int)hd, (int)H,
+                              (int)slabs, cur_stream());
+}
+
 void adv_normalize_op(torch::Tensor adv, torch::Tensor part) {
   check_f32(adv, "adv");
   check_f32(part, "part");
@@ -1260,6 +1350,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("skip_obs") = false, py::arg("ticket") = py::none());
   m.def("ppo_loss_bwd", &ppo_loss_bwd_op, py::arg("head"), py::arg("actions"),
         py::arg("old_logp"), py::arg("adv"), py::arg("ret"), py::arg("dhead"),
+        py::arg("clip_eps"), py::arg("ent_coef"), py::arg("vf_coef"),
+        py::arg("inv_count"), py::arg("losses") = py::none());
+  m.def("head_loss_bwd", &head_loss_bwd_op, py::arg("h2"), py::arg("W3t"),
+        py::arg("W3"), py::arg("b3"), py::arg("actions"), py::arg("old_logp"),
+        py::arg("adv"), py::arg("ret"), py::arg("head"), py::arg("dhead"),
+        py::arg("dh2"), py::arg("dW_part"), py::arg("db_part"), py::arg("dW"),
+        py::arg("db"), py::arg("slabs"), py::arg("reduce"),
         py::arg("clip_eps"), py::arg("ent_coef"), py::arg("vf_coef"),
         py::arg("inv_count"), py::arg("losses") = py::none());
   m.def("adv_normalize", &adv_normalize_op);

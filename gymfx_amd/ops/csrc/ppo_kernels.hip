@@ -23,6 +23,7 @@
 namespace gymfx {
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 GFX_DEV float bf2f(__bf16 v) { return (float)v; }
@@ -1133,6 +1134,52 @@ __global__ void sample_head_kernel(const float* __restrict__ head, int M,
 // losses (logging): [pi_loss, v_loss, entropy, approx_kl, clipfrac] via
 // block-partial + atomicAdd (logging only; gradients are deterministic).
 // ---------------------------------------------------------------------------
+// One row of the loss backward, shared by ppo_loss_bwd_kernel and
+// head_loss_bwd_kernel so both produce the same bits: row = the row's
+// n_actions logits and its value, drow = where its gradient goes.
+GFX_DEV void ppo_loss_row(const float* row, __bf16* drow, int a, float olp,
+                          float A, float rt, int n_actions, float clip_eps,
+                          float ent_coef, float vf_coef, float inv_count,
+                          float& l_pi, float& l_v, float& l_ent, float& l_kl,
+                          float& l_clip) {
+  float mx = row[0];
+  for (int j = 1; j < n_actions; ++j) mx = fmaxf(mx, row[j]);
+  float z = 0.f;
+  for (int j = 0; j < n_actions; ++j) z += expf(row[j] - mx);
+  const float logz = logf(z) + mx;
+  const float lp = row[a] - logz;
+  const float ratio = expf(lp - olp);
+  const bool clipped = (ratio > 1.f + clip_eps) || (ratio < 1.f - clip_eps);
+  const float surr1 = ratio * A;
+  const float rclip = fminf(fmaxf(ratio, 1.f - clip_eps), 1.f + clip_eps);
+  const float surr2 = rclip * A;
+  // d(-min(surr1,surr2))/dlogp = -A*ratio when surr1 <= surr2 (unclipped
+  // branch active), else 0
+  const float g_lp = (surr1 <= surr2) ? (-A * ratio) : 0.f;
+  // entropy bonus: loss += -ent_coef * H
+  float H = 0.f;
+  for (int j = 0; j < n_actions; ++j) {
+    const float lpj = row[j] - logz;
+    H -= expf(lpj) * lpj;
+  }
+  for (int j = 0; j < n_actions; ++j) {
+    const float pj = expf(row[j] - logz);
+    const float onehot = (j == a) ? 1.f : 0.f;
+    float d = g_lp * (onehot - pj);             // policy term
+    d += ent_coef * pj * ((row[j] - logz) + H);  // -ent_coef*dH/dlogit
+    drow[j] = f2bf(d * inv_count);
+  }
+  const float v = row[n_actions];
+  const float dv = vf_coef * (v - rt);
+  drow[n_actions] = f2bf(dv * inv_count);
+
+  l_pi = -fminf(surr1, surr2);
+  l_v = 0.5f * (v - rt) * (v - rt);
+  l_ent = H;
+  l_kl = olp - lp;
+  l_clip = clipped ? 1.f : 0.f;
+}
+
 __global__ void ppo_loss_bwd_kernel(
     const float* __restrict__ head, const int64_t* __restrict__ actions,
     const float* __restrict__ old_logp, const float* __restrict__ adv,
@@ -1141,48 +1188,11 @@ __global__ void ppo_loss_bwd_kernel(
     float inv_count, float* __restrict__ losses) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   float l_pi = 0.f, l_v = 0.f, l_ent = 0.f, l_kl = 0.f, l_clip = 0.f;
-  if (m < M) {
-    const float* row = head + (int64_t)m * (n_actions + 1);
-    __bf16* drow = dhead + (int64_t)m * (n_actions + 1);
-    float mx = row[0];
-    for (int j = 1; j < n_actions; ++j) mx = fmaxf(mx, row[j]);
-    float z = 0.f;
-    for (int j = 0; j < n_actions; ++j) z += expf(row[j] - mx);
-    const float logz = logf(z) + mx;
-    const int a = (int)actions[m];
-    const float lp = row[a] - logz;
-    const float ratio = expf(lp - old_logp[m]);
-    const float A = adv[m];
-    const bool clipped = (ratio > 1.f + clip_eps) || (ratio < 1.f - clip_eps);
-    const float surr1 = ratio * A;
-    const float rclip = fminf(fmaxf(ratio, 1.f - clip_eps), 1.f + clip_eps);
-    const float surr2 = rclip * A;
-    // d(-min(surr1,surr2))/dlogp = -A*ratio when surr1 <= surr2 (unclipped
-    // branch active), else 0
-    const float g_lp = (surr1 <= surr2) ? (-A * ratio) : 0.f;
-    // entropy bonus: loss += -ent_coef * H
-    float H = 0.f;
-    for (int j = 0; j < n_actions; ++j) {
-      const float lpj = row[j] - logz;
-      H -= expf(lpj) * lpj;
-    }
-    for (int j = 0; j < n_actions; ++j) {
-      const float pj = expf(row[j] - logz);
-      const float onehot = (j == a) ? 1.f : 0.f;
-      float d = g_lp * (onehot - pj);             // policy term
-      d += ent_coef * pj * ((row[j] - logz) + H);  // -ent_coef*dH/dlogit
-      drow[j] = f2bf(d * inv_count);
-    }
-    const float v = row[n_actions];
-    const float dv = vf_coef * (v - ret[m]);
-    drow[n_actions] = f2bf(dv * inv_count);
-
-    l_pi = -fminf(surr1, surr2);
-    l_v = 0.5f * (v - ret[m]) * (v - ret[m]);
-    l_ent = H;
-    l_kl = old_logp[m] - lp;
-    l_clip = clipped ? 1.f : 0.f;
-  }
+  if (m < M)
+    ppo_loss_row(head + (int64_t)m * (n_actions + 1),
+                 dhead + (int64_t)m * (n_actions + 1), (int)actions[m],
+                 old_logp[m], adv[m], ret[m], n_actions, clip_eps, ent_coef,
+                 vf_coef, inv_count, l_pi, l_v, l_ent, l_kl, l_clip);
   // block reduction for logging scalars
   __shared__ float red[256];
   float vals[5] = {l_pi, l_v, l_ent, l_kl, l_clip};
@@ -1195,6 +1205,290 @@ __global__ void ppo_loss_bwd_kernel(
     }
     if (threadIdx.x == 0 && losses) atomicAdd(&losses[s], red[0] * inv_count);
     __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------
+// head_loss_bwd_kernel: the head layer of the MLP update in ONE pass over
+// h2 — head GEMM (h2 @ W3 + b3), PPO loss backward, W3/b3 wgrad slab
+// partials and the head dgrad (dh2 = dhead @ W3^T * (1 - h2^2)).  It stands
+// for the launch sequence
+//   gemm_kernel<true,0,false,true,2>      head  = h2 @ W3t^T + b3
+//   ppo_loss_bwd_kernel                   dhead = dL/dhead
+//   wgrad_partial_kernel<true,2,2>        W3/b3 slab partials
+//   gemm_kernel<true,1,true,false,2>      dh2
+// and every output is BITWISE what that sequence writes: each MFMA output
+// element sees the same (a,b) products at the same k positions on top of
+// the same accumulator, in the same order —
+//   head : 8 sequential 16x16x32 steps over k = 0..255, bias added after;
+//   dW3  : one step per 32-row chunk counted from the slab's first row,
+//          reduction index kseg*8+i inside the chunk, rows past the slab
+//          end zero;
+//   dh2  : one step, dhead at k = 0..head_dim-1 and zeros above;
+// the per-row loss math is ppo_loss_row for both kernels.
+//
+// One block owns one wgrad slab (rows [slab*mps, min(M, (slab+1)*mps)),
+// mps = ceil(M/slabs) <= 128) and keeps its h2 rows in LDS: staged once
+// (glds 16 B when the slab is a full 128 rows), read by the head MFMAs, by
+// the transposing wgrad fragment reads and by the tanh' epilogue, which
+// writes dh2 over the h2 element it just read; the tile then leaves with
+// 16 B stores.  The tile is XOR-swizzled in 16 B chunks (chunk c of row r
+// sits at c ^ (r & 15)): rows are 512 B apart, so unswizzled every row of
+// a fragment read would start in the same bank.  glds writes LDS linearly
+// in lane order, so the swizzle is applied to the per-lane SOURCE address.
+// LDS: 64 KB tile + head f32 [128][17] + dhead bf16 [128][16] = 76.5 KB,
+// two blocks per CU.
+// ---------------------------------------------------------------------------
+constexpr int kHlbRows = 128;   // rows per block (max m_per_slab)
+constexpr int kHlbHid = 256;    // hidden width (tile row length)
+constexpr int kHlbHead = 16;    // max head_dim (one MFMA n/k fragment)
+constexpr int kHlbHdLd = kHlbHead + 1;  // head f32 row stride (bank spread)
+constexpr int kLossShardLd = 32;  // floats per logging-sum shard: one 128 B line
+
+// element offset of (row r, column col) in the swizzled h2 tile
+GFX_DEV int hlb_off(int r, int col) {
+  const int c = col >> 3;
+  return r * kHlbHid + (((c & 16) | ((c ^ r) & 15)) << 3) + (col & 7);
+}
+
+__global__ __launch_bounds__(256, 2) void head_loss_bwd_kernel(
+    const __bf16* __restrict__ h2, const __bf16* __restrict__ W3t,
+    const __bf16* __restrict__ W3, const float* __restrict__ b3,
+    const int64_t* __restrict__ actions, const float* __restrict__ old_logp,
+    const float* __restrict__ adv, const float* __restrict__ ret,
+    float* __restrict__ head, __bf16* __restrict__ dhead,
+    __bf16* __restrict__ dh2, float* __restrict__ dW_part,
+    float* __restrict__ db_part, int M, int head_dim, int slabs,
+    float clip_eps, float ent_coef, float vf_coef, float inv_count,
+    float* __restrict__ losses, int loss_shards) {
+  // ONE shared object (a second one beside a glds target can make the
+  // compiler drain vmcnt before every LDS read)
+  constexpr int kTileBytes = kHlbRows * kHlbHid * 2;
+  constexpr int kHdBytes = kHlbRows * kHlbHdLd * 4;
+  constexpr int kDsBytes = kHlbRows * kHlbHead * 2;
+  __shared__ __align__(16) unsigned char smem[kTileBytes + kHdBytes + kDsBytes];
+  __bf16* Hs = reinterpret_cast<__bf16*>(smem);                  // h2 / dh2
+  float* Hd = reinterpret_cast<float*>(smem + kTileBytes);       // head
+  __bf16* Ds = reinterpret_cast<__bf16*>(smem + kTileBytes + kHdBytes);
+
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int row_a = lane & 15;
+  const int kseg = lane >> 4;
+  const int crow_base = (lane >> 4) * 4;
+  const int ccol = lane & 15;
+
+  const int slab = blockIdx.x;
+  const int m_per_slab = (M + slabs - 1) / slabs;
+  const int m_begin = slab * m_per_slab;
+  const int m_end = min(M, m_begin + m_per_slab);
+  const int nrows = max(0, m_end - m_begin);        // <= kHlbRows (launcher)
+  const int rpad = min(kHlbRows, (nrows + 31) & ~31);  // rows the MFMAs touch
+  const int n_actions = head_dim - 1;
+
+  // ---- stage ----------------------------------------------------------
+  // W3t fragments for the head GEMM: B[k][col] = W3t[col][k], zero columns
+  // past head_dim (what the GEMM's guarded staging puts in its tile)
+  bf16x8 bh[kHlbHid / 32];
+#pragma unroll
+  for (int ks = 0; ks < kHlbHid / 32; ++ks) {
+    bh[ks] = bf16x8{};
+    if (row_a < head_dim)
+      bh[ks] = *reinterpret_cast<const bf16x8*>(
+          &W3t[row_a * kHlbHid + ks * 32 + kseg * 8]);
+  }
+  // dhead image: zero everywhere the loss does not write (k/n padding of
+  // the MFMA operands, rows past the slab end)
+  *reinterpret_cast<bf16x8*>(&Ds[tid * 8]) = bf16x8{};
+  if (nrows == kHlbRows) {
+    // 64 KB = 64 glds instructions of 1 KB, 16 per wave
+    for (int j = 0; j < 16; ++j) {
+      const int e0 = (wave * 16 + j) * 512;
+      const int e = e0 + lane * 8;
+      const int r = e >> 8;
+      const int p = (e >> 3) & 31;
+      const int c = (p & 16) | ((p ^ r) & 15);
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) void*)(uintptr_t)(
+              &h2[(int64_t)(m_begin + r) * kHlbHid + c * 8]),
+          (__attribute__((address_space(3))) void*)(uintptr_t)(Hs + e0), 16, 0,
+          0);
+    }
+  } else {
+    for (int idx = tid; idx < rpad * 32; idx += 256) {
+      const int r = idx >> 5;
+      const int p = idx & 31;
+      const int c = (p & 16) | ((p ^ r) & 15);
+      bf16x8 v = bf16x8{};
+      if (r < nrows)
+        v = *reinterpret_cast<const bf16x8*>(
+            &h2[(int64_t)(m_begin + r) * kHlbHid + c * 8]);
+      *reinterpret_cast<bf16x8*>(&Hs[idx * 8]) = v;
+    }
+  }
+  __syncthreads();  // vmcnt(0) inside the barrier drains the glds
+
+  // ---- head = h2 @ W3t^T + b3 (wave w: rows w*32 .. w*32+31) ------------
+  if (wave * 32 < rpad) {
+    for (int mi = 0; mi < 2; ++mi) {
+      const int r0 = wave * 32 + mi * 16;
+      f32x4 acc = {};
+#pragma unroll
+      for (int ks = 0; ks < kHlbHid / 32; ++ks) {  // sequential k order
+        const bf16x8 af = *reinterpret_cast<const bf16x8*>(
+            &Hs[hlb_off(r0 + row_a, ks * 32 + kseg * 8)]);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bh[ks], acc, 0, 0, 0);
+      }
+      if (ccol < head_dim) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float v = acc[r];
+          v += b3[ccol];
+          Hd[(r0 + crow_base + r) * kHlbHdLd + ccol] = v;
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- loss backward: one thread per row -------------------------------
+  {
+    float l_pi = 0.f, l_v = 0.f, l_ent = 0.f, l_kl = 0.f, l_clip = 0.f;
+    if (tid < nrows) {
+      const int m = m_begin + tid;
+      ppo_loss_row(Hd + tid * kHlbHdLd, Ds + tid * kHlbHead, (int)actions[m],
+                   old_logp[m], adv[m], ret[m], n_actions, clip_eps, ent_coef,
+                   vf_coef, inv_count, l_pi, l_v, l_ent, l_kl, l_clip);
+    }
+    // logging sums: wave shuffle reduce, one atomicAdd per stat per wave,
+    // into accumulator row slab % loss_shards (rows kLossShardLd floats
+    // apart).  Device-scope float atomics on ONE cache line retire at about
+    // 88 per us whatever the word, so the 5120 of a 512-block launch on a
+    // single [5] accumulator take 58 us; spread over 64 lines they are free.
+    if (losses && wave * 64 < nrows) {
+      losses += (slab % loss_shards) * kLossShardLd;
+      float vals[5] = {l_pi, l_v, l_ent, l_kl, l_clip};
+#pragma unroll
+      for (int s = 0; s < 5; ++s) {
+        float x = vals[s];
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+        if (lane == 0) atomicAdd(&losses[s], x * inv_count);
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- head / dhead out (the slab's rows are contiguous in both) --------
+  for (int idx = tid; idx < nrows * head_dim; idx += 256) {
+    const int r = idx / head_dim;
+    const int j = idx - r * head_dim;
+    head[(int64_t)m_begin * head_dim + idx] = Hd[r * kHlbHdLd + j];
+    dhead[(int64_t)m_begin * head_dim + idx] = Ds[r * kHlbHead + j];
+  }
+
+  // W3 fragments for the dgrad: B[k][n] = W3[n][k], k < head_dim
+  // (wave w: columns w*64 .. w*64+63)
+  bf16x8 bw[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    bw[g] = bf16x8{};
+    const int n = (wave * 4 + g) * 16 + row_a;
+    // every load issued (index clamped in bounds), then masked: a branch
+    // around each load would wait for them one by one
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int k = kseg * 8 + i;
+      const __bf16 w = W3[n * head_dim + min(k, head_dim - 1)];
+      bw[g][i] = (k < head_dim) ? w : (__bf16)0.f;
+    }
+  }
+
+  // ---- W3 / b3 slab partials (wave w: dW rows w*64 .. w*64+63) ----------
+  {
+    const int nchunks = (nrows + 31) / 32;
+    f32x4 acc[4] = {};
+    for (int ci = 0; ci < nchunks; ++ci) {
+      const int m0 = ci * 32 + kseg * 8;  // reduction index kseg*8+i
+      bf16x8 bf_;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) bf_[i] = Ds[(m0 + i) * kHlbHead + row_a];
+#pragma unroll
+      for (int f = 0; f < 4; ++f) {
+        bf16x8 af;
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          af[i] = Hs[hlb_off(m0 + i, (wave * 4 + f) * 16 + row_a)];
+        acc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf_, acc[f], 0, 0,
+                                                         0);
+      }
+    }
+    float* out = dW_part + (int64_t)slab * kHlbHid * head_dim;
+    if (ccol < head_dim) {
+#pragma unroll
+      for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int grow = (wave * 4 + f) * 16 + crow_base + r;
+          out[grow * head_dim + ccol] = acc[f][r];
+        }
+    }
+    if (tid < head_dim) {
+      float db_acc = 0.f;
+      for (int ci = 0; ci < nchunks; ++ci) {
+        // row order, as wgrad_partial_kernel sums it; rows past the slab
+        // end are zero in Ds, and s + 0.f leaves s (never -0.f: it starts
+        // at +0.f) as it is, so the chunk is read whole, loads first
+        float x[32];
+#pragma unroll
+        for (int i = 0; i < 32; ++i)
+          x[i] = bf2f(Ds[(ci * 32 + i) * kHlbHead + tid]);
+        float s = 0.f;
+#pragma unroll
+        for (int i = 0; i < 32; ++i) s += x[i];
+        db_acc += s;
+      }
+      db_part[(int64_t)slab * head_dim + tid] = db_acc;
+    }
+  }
+  __syncthreads();  // every h2 read of the wgrad is done: dh2 may overwrite
+
+  // ---- dh2 = dhead @ W3^T * (1 - h2^2), written over the h2 tile --------
+  // The MFMA computes the TRANSPOSED fragment (W3 as the A operand, dhead
+  // as B: the same products at the same k positions), so a lane holds four
+  // consecutive columns of one row and the epilogue moves 8 B per LDS access
+  // instead of 2.
+  for (int mi = 0; mi < rpad / 16; ++mi) {
+    bf16x8 df = bf16x8{};
+    if (kseg < kHlbHead / 8)
+      df = *reinterpret_cast<const bf16x8*>(
+          &Ds[(mi * 16 + row_a) * kHlbHead + kseg * 8]);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          bw[g], df, f32x4{}, 0, 0, 0);
+      // acc[r]: column (wave*4+g)*16 + crow_base + r of row mi*16 + ccol
+      bf16x4* yp = reinterpret_cast<bf16x4*>(
+          &Hs[hlb_off(mi * 16 + ccol, (wave * 4 + g) * 16 + crow_base)]);
+      const bf16x4 yv = *yp;
+      bf16x4 ov;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        float v = acc[r];
+        float y = bf2f(yv[r]);
+        v *= (1.f - y * y);
+        ov[r] = f2bf(v);
+      }
+      *yp = ov;
+    }
+  }
+  __syncthreads();
+
+  for (int idx = tid; idx < nrows * 32; idx += 256) {
+    const int r = idx >> 5;
+    const int p = idx & 31;
+    const int c = (p & 16) | ((p ^ r) & 15);
+    *reinterpret_cast<bf16x8*>(&dh2[(int64_t)(m_begin + r) * kHlbHid + c * 8]) =
+        *reinterpret_cast<const bf16x8*>(&Hs[idx * 8]);
   }
 }
 
@@ -2405,6 +2699,9 @@ void launch_gemm(const void* A, const void* B, const float* bias, void* C,
 #undef GEMM_LAUNCH
 }
 
+void launch_slab_reduce(const float* dW_part, const float* db_part, float* dW,
+                        float* db, int N, int K, int slabs, hipStream_t stream);
+
 void launch_wgrad(const void* X, const void* dY, float* dW_part, float* db_part,
                   float* dW, float* db, int M, int N, int K, int slabs,
                   hipStream_t stream, const FeistelMap* fmp = nullptr,
@@ -2493,6 +2790,15 @@ void launch_wgrad(const void* X, const void* dY, float* dW_part, float* db_part,
   // reduce == false: the partials stay in dW_part/db_part and
   // launch_grads_finalize reduces every layer's workspace in one launch
   if (!reduce) return;
+  launch_slab_reduce(dW_part, db_part, dW, db, N, K, slabs, stream);
+}
+
+// The reduce half of launch_wgrad on its own: slab partials -> dW/db (also
+// run on the partials head_loss_bwd_kernel wrote when the fused optimizer
+// tail is off).
+void launch_slab_reduce(const float* dW_part, const float* db_part, float* dW,
+                        float* db, int N, int K, int slabs,
+                        hipStream_t stream) {
   int64_t elems = (int64_t)K * N;
   if (elems <= 4096) {
     hipLaunchKernelGGL(slab_reduce_small_kernel, dim3((int)elems), dim3(256),
@@ -2592,6 +2898,27 @@ void launch_ppo_loss_bwd(const float* head, const int64_t* actions,
                      stream, head, actions, old_logp, adv, ret,
                      reinterpret_cast<__bf16*>(dhead), M, n_actions, clip_eps,
                      ent_coef, vf_coef, inv_count, losses);
+}
+
+// hidden == 256, head_dim <= 16 and ceil(M/slabs) <= 128 are the caller's
+// to check (bindings.cpp: head_loss_bwd_op)
+void launch_head_loss_bwd(const void* h2, const void* W3t, const void* W3,
+                          const float* b3, const int64_t* actions,
+                          const float* old_logp, const float* adv,
+                          const float* ret, float* head, void* dhead,
+                          void* dh2, float* dW_part, float* db_part, int M,
+                          int head_dim, int slabs, float clip_eps,
+                          float ent_coef, float vf_coef, float inv_count,
+                          float* losses, int loss_shards, hipStream_t stream) {
+  hipLaunchKernelGGL(head_loss_bwd_kernel, dim3(slabs), dim3(256), 0, stream,
+                     reinterpret_cast<const __bf16*>(h2),
+                     reinterpret_cast<const __bf16*>(W3t),
+                     reinterpret_cast<const __bf16*>(W3), b3, actions,
+                     old_logp, adv, ret, head,
+                     reinterpret_cast<__bf16*>(dhead),
+                     reinterpret_cast<__bf16*>(dh2), dW_part, db_part, M,
+                     head_dim, slabs, clip_eps, ent_coef, vf_coef, inv_count,
+                     losses, loss_shards);
 }
 
 void launch_adv_normalize(float* adv, int64_t n, float* part, int nparts,
