@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "env_common.h"
+#include "mfma_dispatch.h"
 
 namespace gymfx {
 
@@ -1256,6 +1257,43 @@ void transpose_bf16_op(torch::Tensor src, torch::Tensor dst) {
                                cur_stream());
 }
 
+
+// ---- dispatch queries (host only: nothing here touches the GPU) ----------
+// knob arguments: None = the value this process read from its environment,
+// an integer = "what would be launched under this knob" (-1 = unset)
+int knob_or(const c10::optional<int64_t>& v, int process_value) {
+  return v.has_value() ? (int)*v : process_value;
+}
+
+py::tuple gemm_variant_op(int64_t M, int64_t N, int64_t K, bool trans_b,
+                          int64_t act, bool dact_tanh, bool add_bias,
+                          bool accum, bool a_perm,
+                          c10::optional<int64_t> wide,
+                          c10::optional<int64_t> bk64,
+                          c10::optional<int64_t> n1) {
+  const gymfx::GemmKnobs& pk = gymfx::process_gemm_knobs();
+  gymfx::GemmKnobs kn;
+  kn.wide = knob_or(wide, pk.wide);
+  kn.bk64 = knob_or(bk64, pk.bk64);
+  kn.n1 = knob_or(n1, pk.n1);
+  const gymfx::GemmSel s =
+      gymfx::select_gemm((int)M, (int)N, (int)K, trans_b, (int)act, dact_tanh,
+                         add_bias, accum, a_perm, kn);
+  TORCH_CHECK(gymfx::gemm_instantiated(s), "no gemm kernel instantiated for ",
+              gymfx::gemm_name(s));
+  return py::make_tuple(gymfx::gemm_name(s), py::make_tuple(s.gx, s.gy));
+}
+
+py::tuple wgrad_variant_op(int64_t M, int64_t N, int64_t K, int64_t slabs,
+                           bool want_db, bool x_perm,
+                           c10::optional<int64_t> big) {
+  const gymfx::WgradSel s = gymfx::select_wgrad(
+      (int)M, (int)N, (int)K, (int)slabs, want_db, x_perm,
+      knob_or(big, gymfx::process_wgrad_big_knob()));
+  return py::make_tuple(gymfx::wgrad_name(s),
+                        py::make_tuple(s.gx, s.gy, s.gz));
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1362,6 +1400,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("adv_normalize", &adv_normalize_op);
   m.def("f32_to_bf16", &f32_to_bf16_op);
   m.def("transpose_bf16", &transpose_bf16_op);
+  m.def("gemm_variant", &gemm_variant_op,
+        "(name, (gx, gy)) of the gemm_kernel instantiation launch_gemm picks; "
+        "knobs left None take this process's GYMFX_GEMM_* values",
+        py::arg("M"), py::arg("N"), py::arg("K"), py::arg("trans_b") = false,
+        py::arg("act") = 1, py::arg("dact_tanh") = false,
+        py::arg("add_bias") = false, py::arg("accum") = false,
+        py::arg("a_perm") = false, py::arg("wide") = py::none(),
+        py::arg("bk64") = py::none(), py::arg("n1") = py::none());
+  m.def("wgrad_variant", &wgrad_variant_op,
+        "(name, (gx, gy, gz)) of the wgrad kernel launch_wgrad picks; "
+        "big=None takes this process's GYMFX_WGRAD_BIG value",
+        py::arg("M"), py::arg("N"), py::arg("K"), py::arg("slabs"),
+        py::arg("want_db") = true, py::arg("x_perm") = false,
+        py::arg("big") = py::none());
+  m.def("mfma_variants", &gymfx::mfma_variant_names,
+        "names of every instantiated gemm / wgrad kernel variant");
   py::class_<gymfx::GymFxEngine>(m, "GymFxEngine")
       .def(py::init<const py::dict&, const py::dict&, const py::dict&, const py::dict&>())
       .def("step", &gymfx::GymFxEngine::step, py::arg("actions"),

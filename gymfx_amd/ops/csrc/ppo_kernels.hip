@@ -15,6 +15,7 @@
 // Verified on hardware by tests/test_gpu_gemm.py (identity x asymmetric-B
 // probes per guide rule G9).
 #include "env_common.h"
+#include "mfma_dispatch.h"
 
 #include <hip/hip_bf16.h>
 
@@ -2594,109 +2595,25 @@ void launch_gemm(const void* A, const void* B, const float* bias, void* C,
   const __bf16* a = reinterpret_cast<const __bf16*>(A);
   const __bf16* b = reinterpret_cast<const __bf16*>(B);
   const __bf16* y = reinterpret_cast<const __bf16*>(Yact);
-  // Tile width: 64x64 (NFRAG=2) tiles run at occupancy 8 and beat the
-  // 64x256 (NFRAG=8, occupancy 3) wide tiles even at tall update shapes
-  // (M=65536: 20.3 vs 22.0 ms/update whole-trainer) — the extra occupancy
-  // hides HBM latency better than wide tiles save A-operand re-streaming
-  // (L2 absorbs the re-reads).  GYMFX_GEMM_WIDE=1 forces the wide tile,
-  // =4 the 64x128 middle tile (tuning knobs).
-  static const int wide_env = [] {
-    const char* e = getenv("GYMFX_GEMM_WIDE");
-    return e ? atoi(e) : -1;
-  }();
-  // BK=64 staging pipeline (half the barriers) for long-K trans_b shapes —
-  // ROADMAP lever 2; GYMFX_GEMM_BK64=1 forces on, =0 forces off
-  static const int bk64_env = [] {
-    const char* e = getenv("GYMFX_GEMM_BK64");
-    return e ? atoi(e) : -1;
-  }();
-  // Tile-width heuristic: at N >= 1024 the 64-wide tile re-streams the A
-  // operand N/64 times (the LSTM Wx gates GEMM read its 34 MB A slab 16x
-  // = 544 MB/call); the 64x256 tile cuts that 4x and wins big there.
-  // The round-1 "wide loses" measurement holds only for N <= 256 outputs.
-  const bool mid = (N >= 96) &&
-                   (wide_env == 4 ||
-                    (wide_env == -1 && N >= 1024 && M >= 16384));
-  const bool wide = (N >= 192) && !mid && wide_env == 1;
-  // measured: BK=64 wins for long-K shapes (LSTM dgates dgrad K=1024:
-  // update 41.5 -> 39.9 ms) and LOSES at K<=260 (MLP headline 28.4 ->
-  // 27.4M) — auto-enable only at K >= 512
-  const bool bk64 = trans_b && !wide && !mid &&
-                    (bk64_env == 1 || (bk64_env != 0 && K >= 512));
-  dim3 grid(ceil_div(M, 64), ceil_div(N, wide ? 256 : (mid ? 128 : 64)));
-  dim3 block(256);
-  // Narrow 64x32 tile (NFRAG=1, BK=64 only — see the BLPT static_assert):
-  // at N=256 the 64x64 tile fills exactly 1 block/CU (the LSTM bwd-chain
-  // dgrad: 64x4 = 256 workgroups) while occupancy allows more; BN=32
-  // doubles the grid for latency hiding at 2x B re-streaming.
-  // GYMFX_GEMM_N1=1 forces on, =0 off, unset = auto (M*N small, long K).
-  static const int n1_env = [] {
-    const char* e = getenv("GYMFX_GEMM_N1");
-    return e ? atoi(e) : -1;
-  }();
-  if (bk64 && act == 0 && !dact_tanh && !add_bias && !accum && !fmp &&
-      N <= 256 &&
-      (n1_env == 1 || (n1_env == -1 && (int64_t)M * N <= 64 * 64 * 256))) {
-    dim3 grid_n1(ceil_div(M, 64), ceil_div(N, 32));
-    hipLaunchKernelGGL((gemm_kernel<true, 0, false, false, 1, false, 64>),
-                       grid_n1, block, 0, stream, a, b, bias, C, y, M, N, K);
-    return;
+  // tile choice and grid: select_gemm (mfma_dispatch.h), with the knobs
+  // this process read from its environment
+  const GemmSel s = select_gemm(M, N, K, trans_b, act, dact_tanh, add_bias,
+                                accum, fmp != nullptr, process_gemm_knobs());
+  const dim3 grid(s.gx, s.gy), block(256);
+  const FeistelMap fm = fmp ? *fmp : FeistelMap{};
+#define GYMFX_X(TB, ACT, DT, AB, NF, ACC, BK, PERM)                           \
+  if (gemm_sel_is(s, TB, ACT, DT, AB, NF, ACC, BK, PERM)) {                   \
+    hipLaunchKernelGGL((gemm_kernel<TB, ACT, DT, AB, NF, ACC, BK, PERM>),     \
+                       grid, block, 0, stream, a, b, bias, C, y, M, N, K,     \
+                       fm);                                                   \
+    return;                                                                   \
   }
-  if (fmp) {
-    // gather+first-GEMM fusion: only the L1 forward combo is instantiated
-    // (trans_b, tanh epilogue, bias, 64x64 tile)
-    if (!(trans_b && act == 2 && !dact_tanh && add_bias && !accum)) {
-      // unreachable by construction (models/mlp.py passes a_feistel only
-      // on the first layer); abort loudly if it ever is
-      abort();
-    }
-    hipLaunchKernelGGL((gemm_kernel<true, 2, false, true, 2, false, 32, true>),
-                       grid, block, 0, stream, a, b, bias, C, y, M, N, K,
-                       *fmp);
-    return;
-  }
-
-#define GEMM_LAUNCH(TB, ACT, DT, AB)                                          \
-  do {                                                                        \
-    if (wide)                                                                 \
-      hipLaunchKernelGGL((gemm_kernel<TB, ACT, DT, AB, 8>), grid, block, 0,   \
-                         stream, a, b, bias, C, y, M, N, K);                  \
-    else if (mid)                                                             \
-      hipLaunchKernelGGL((gemm_kernel<TB, ACT, DT, AB, 4>), grid, block, 0,   \
-                         stream, a, b, bias, C, y, M, N, K);                  \
-    else if (bk64)                                                            \
-      hipLaunchKernelGGL((gemm_kernel<TB, ACT, DT, AB, 2, false, 64>), grid,  \
-                         block, 0, stream, a, b, bias, C, y, M, N, K);        \
-    else                                                                      \
-      hipLaunchKernelGGL((gemm_kernel<TB, ACT, DT, AB, 2>), grid, block, 0,   \
-                         stream, a, b, bias, C, y, M, N, K);                  \
-  } while (0)
-  if (accum) {
-    // C += A@B (f32 out, no bias/activation): the LSTM recurrent GEMM
-    if (trans_b)
-      if (wide) hipLaunchKernelGGL((gemm_kernel<true, 0, false, false, 8, true>), grid, block, 0, stream, a, b, bias, C, y, M, N, K);
-      else if (mid) hipLaunchKernelGGL((gemm_kernel<true, 0, false, false, 4, true>), grid, block, 0, stream, a, b, bias, C, y, M, N, K);
-      else hipLaunchKernelGGL((gemm_kernel<true, 0, false, false, 2, true>), grid, block, 0, stream, a, b, bias, C, y, M, N, K);
-    else
-      if (wide) hipLaunchKernelGGL((gemm_kernel<false, 0, false, false, 8, true>), grid, block, 0, stream, a, b, bias, C, y, M, N, K);
-      else if (mid) hipLaunchKernelGGL((gemm_kernel<false, 0, false, false, 4, true>), grid, block, 0, stream, a, b, bias, C, y, M, N, K);
-      else hipLaunchKernelGGL((gemm_kernel<false, 0, false, false, 2, true>), grid, block, 0, stream, a, b, bias, C, y, M, N, K);
-    return;
-  }
-  if (!trans_b && !dact_tanh) {
-    if (act == 0) { if (add_bias) GEMM_LAUNCH(false, 0, false, true); else GEMM_LAUNCH(false, 0, false, false); }
-    else if (act == 1) { if (add_bias) GEMM_LAUNCH(false, 1, false, true); else GEMM_LAUNCH(false, 1, false, false); }
-    else { if (add_bias) GEMM_LAUNCH(false, 2, false, true); else GEMM_LAUNCH(false, 2, false, false); }
-  } else if (trans_b && !dact_tanh) {
-    if (act == 0) { if (add_bias) GEMM_LAUNCH(true, 0, false, true); else GEMM_LAUNCH(true, 0, false, false); }
-    else if (act == 1) { if (add_bias) GEMM_LAUNCH(true, 1, false, true); else GEMM_LAUNCH(true, 1, false, false); }
-    else { if (add_bias) GEMM_LAUNCH(true, 2, false, true); else GEMM_LAUNCH(true, 2, false, false); }
-  } else if (trans_b && dact_tanh) {
-    GEMM_LAUNCH(true, 1, true, false);
-  } else {
-    GEMM_LAUNCH(false, 1, true, false);
-  }
-#undef GEMM_LAUNCH
+  GYMFX_GEMM_VARIANTS(GYMFX_X)
+#undef GYMFX_X
+  // no kernel for this flag combination (a_perm with anything but the L1
+  // forward epilogue): unreachable by construction, abort loudly if it
+  // ever is
+  abort();
 }
 
 void launch_slab_reduce(const float* dW_part, const float* db_part, float* dW,
@@ -2708,85 +2625,31 @@ void launch_wgrad(const void* X, const void* dY, float* dW_part, float* db_part,
                   bool reduce = true) {
   const __bf16* x = reinterpret_cast<const __bf16*>(X);
   const __bf16* dy = reinterpret_cast<const __bf16*>(dY);
-  // Tile choice: 128x128 halves the HBM re-streaming of X/dY — wgrad runs
-  // at ~5.7 TB/s with 64x64 tiles, i.e. bandwidth-bound, so the bigger tile
-  // wins whenever the grid still fills the chip (MLP 260x256 shapes:
-  // 19.3 -> 18.5 ms/update whole-trainer).  384+ workgroups = 1.5 waves/SIMD
-  // at the kernel's occupancy 2 keeps every CU fed.
-  // GYMFX_WGRAD_BIG=0/1 overrides (tuning knob).
-  static const int big_env = [] {
-    const char* e = getenv("GYMFX_WGRAD_BIG");
-    return e ? atoi(e) : -1;
-  }();
-  const bool big = K >= 128 && N >= 128 &&
-                   (big_env >= 0
-                        ? big_env != 0
-                        : (int64_t)ceil_div(K, 128) * ceil_div(N, 128) * slabs >=
-                              384);
-  const int m_per_slab = (M + slabs - 1) / slabs;
-  // glds path (both tile configs): full tiles only; the K tail runs the
-  // skinny per-slab streaming kernel.
-  const int TW = big ? 128 : 64;
-  const bool glds_ok = N % TW == 0 && K >= TW && m_per_slab % 64 == 0 &&
-                       M % slabs == 0;
-  (void)0;
-  if (glds_ok) {
-    // the glds kernel masks a partial final K tile in-kernel (guarded
-    // register staging + grow<K epilogue guard), so NO separate tail pass
-    // over dY is needed.  For K=260 the 5x4 tile (TK=160) covers K in TWO
-    // passes where 128-wide tiles need three — one fewer full dY read
-    // (~1.5 ms/update on the LSTM wgrads).
-#define WG_GLDS(WDB, FK, FN, GRID)                                            \
-  do {                                                                        \
-    if (fmp)                                                                  \
-      hipLaunchKernelGGL((wgrad_glds_kernel<WDB, FK, FN, true>), GRID,        \
-                         dim3(256), 0, stream, x, dy, dW_part, db_part, M, N, \
-                         K, slabs, *fmp);                                     \
-    else                                                                      \
-      hipLaunchKernelGGL((wgrad_glds_kernel<WDB, FK, FN>), GRID, dim3(256),   \
-                         0, stream, x, dy, dW_part, db_part, M, N, K, slabs); \
-  } while (0)
-    if (big) {
-      // 5x4 (TK=160) saves a dY pass for K=260 but its 80-VGPR accs spill
-      // at N >= 1024 (LSTM Wx wgrad measured 187 us vs 144 for 4x4+tail)
-      const int t44 = ceil_div(K, 128), t54 = ceil_div(K, 160);
-      if (t54 < t44 && N <= 512) {
-        dim3 g0(t54, N / TW, slabs);
-        if (db_part) WG_GLDS(true, 5, 4, g0);
-        else WG_GLDS(false, 5, 4, g0);
-      } else {
-        dim3 g0(t44, N / TW, slabs);
-        if (db_part) WG_GLDS(true, 4, 4, g0);
-        else WG_GLDS(false, 4, 4, g0);
-      }
-    } else {
-      dim3 g0(ceil_div(K, 64), N / TW, slabs);
-      if (db_part) WG_GLDS(true, 2, 2, g0);
-      else WG_GLDS(false, 2, 2, g0);
-    }
-#undef WG_GLDS
-  } else {
-    dim3 grid(ceil_div(K, big ? 128 : 64), ceil_div(N, big ? 128 : 64), slabs);
-#define WG_PART(WDB, FK, FN)                                                  \
-  do {                                                                        \
-    if (fmp)                                                                  \
-      hipLaunchKernelGGL((wgrad_partial_kernel<WDB, FK, FN, true>), grid,     \
-                         dim3(256), 0, stream, x, dy, dW_part, db_part, M, N, \
-                         K, slabs, 0, *fmp);                                  \
-    else                                                                      \
-      hipLaunchKernelGGL((wgrad_partial_kernel<WDB, FK, FN>), grid,           \
-                         dim3(256), 0, stream, x, dy, dW_part, db_part, M, N, \
-                         K, slabs, 0);                                        \
-  } while (0)
-    if (db_part) {
-      if (big) WG_PART(true, 4, 4);
-      else WG_PART(true, 2, 2);
-    } else {
-      if (big) WG_PART(false, 4, 4);
-      else WG_PART(false, 2, 2);
-    }
-#undef WG_PART
+  // tile choice and grid: select_wgrad (mfma_dispatch.h)
+  const WgradSel s = select_wgrad(M, N, K, slabs, db_part != nullptr,
+                                  fmp != nullptr, process_wgrad_big_knob());
+  const dim3 grid(s.gx, s.gy, s.gz);
+  const FeistelMap fm = fmp ? *fmp : FeistelMap{};
+  bool launched = false;
+#define GYMFX_X(DB, FK, FN, PERM)                                             \
+  if (wgrad_sel_is(s, true, DB, FK, FN, PERM)) {                              \
+    hipLaunchKernelGGL((wgrad_glds_kernel<DB, FK, FN, PERM>), grid,           \
+                       dim3(256), 0, stream, x, dy, dW_part, db_part, M, N,   \
+                       K, slabs, fm);                                         \
+    launched = true;                                                          \
   }
+  GYMFX_WGRAD_GLDS_VARIANTS(GYMFX_X)
+#undef GYMFX_X
+#define GYMFX_X(DB, FK, FN, PERM)                                             \
+  if (wgrad_sel_is(s, false, DB, FK, FN, PERM)) {                             \
+    hipLaunchKernelGGL((wgrad_partial_kernel<DB, FK, FN, PERM>), grid,        \
+                       dim3(256), 0, stream, x, dy, dW_part, db_part, M, N,   \
+                       K, slabs, 0, fm);                                      \
+    launched = true;                                                          \
+  }
+  GYMFX_WGRAD_PARTIAL_VARIANTS(GYMFX_X)
+#undef GYMFX_X
+  if (!launched) abort();  // select_wgrad returned a tile with no kernel
   // reduce == false: the partials stay in dW_part/db_part and
   // launch_grads_finalize reduces every layer's workspace in one launch
   if (!reduce) return;
