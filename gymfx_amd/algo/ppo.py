@@ -89,6 +89,16 @@ class PPOConfig:
                                  # slab; other shapes keep the four launches).
                                  # Bitwise == the four-launch sequence
                                  # (tests/test_gpu_head_bwd.py).  MLP only.
+    resident_gemm: bool = True   # the tall N=256 GEMMs of the MLP update
+                                 # (L1/L2 forward, L2 dgrad) run the weight-
+                                 # resident kernel: weights loaded into LDS
+                                 # once per workgroup, A read once.  Bitwise ==
+                                 # the tiled kernel
+                                 # (tests/test_gpu_resident_gemm.py).  Only
+                                 # calls with >= resident_min_rows rows are
+                                 # routed: rollout and serving keep the tiled
+                                 # kernel.  MLP only.
+    resident_min_rows: int = 65536  # measured crossover, PERF_NOTES.md
 
     @classmethod
     def from_config(cls, cfg: Dict[str, Any]) -> "PPOConfig":
@@ -117,6 +127,8 @@ class PPOConfig:
             "overlap_gather": "overlap_gather",
             "fused_opt_tail": "fused_opt_tail",
             "fused_head_bwd": "fused_head_bwd",
+            "resident_gemm": "resident_gemm",
+            "resident_min_rows": "resident_min_rows",
         }
         from ..config.merger import convert_type
 
@@ -290,6 +302,10 @@ class PPOTrainer:
         # the feed-forward trainer's materialized-minibatch paths (the
         # _fuse_gather branch of _fwd_bwd_body keeps its own sequence)
         self._fused_head = bool(cfg.fused_head_bwd) and not self.recurrent
+        # weight-resident tall GEMMs of the MLP update (models/mlp.py)
+        if not self.recurrent:
+            self.model.resident_gemm = bool(cfg.resident_gemm)
+            self.model.resident_min_rows = int(cfg.resident_min_rows)
         # its logging sums go to 64 accumulator rows on separate cache lines
         # (api.head_loss_bwd) and update() folds them into self.losses once
         self._loss_shards = (

@@ -93,6 +93,9 @@ DEFAULT_VALUES = {
     "overlap_gather": False,     # side-stream mb gather (measured slower)
     "fused_opt_tail": True,      # 2-launch reduce/optimizer tail per minibatch
     "fused_head_bwd": True,      # head fwd + loss bwd + head bwd in one kernel
+    "resident_gemm": True,       # weight-resident kernel for the tall N=256
+                                 # update GEMMs (MLP) ...
+    "resident_min_rows": 65536,  # ... of calls with at least this many rows
     "checkpoint_file": None,     # save/resume path (mode=training)
     "checkpoint_interval": 0,    # save every N updates (0 = final only)
     "resume": False,

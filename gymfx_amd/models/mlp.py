@@ -101,8 +101,17 @@ class ActorCriticMLP:
         self.fuse_norm = False
         self._adam_ticket = torch.zeros((), dtype=torch.int32, device=device)
         self._fin_segs = None
+        # weight-resident tall GEMM (PPOConfig.resident_gemm): the N=hidden
+        # layers of calls with at least resident_min_rows rows ask api.gemm
+        # for the resident kernel (bitwise equal; it wins only when the 256-
+        # row groups fill the chip, so rollout/serving batches stay tiled)
+        self.resident_gemm = False
+        self.resident_min_rows = 65536
 
     # -- param views ----------------------------------------------------
+    def _resident(self, M: int) -> bool:
+        return self.resident_gemm and M >= self.resident_min_rows
+
     def w(self, name: str) -> torch.Tensor:
         s = self.slices[name]
         return self.params_bf16[s.sl].view(*s.shape)
@@ -187,9 +196,11 @@ class ActorCriticMLP:
         vector staging on gfx950 regardless of tile width.
         a_feistel: gather+first-GEMM fusion — obs_bf16 is the FULL rollout
         slab and L1 reads its rows through the epoch permutation."""
+        res = self._resident(acts["h1"].shape[0])
         api.gemm(obs_bf16, self.wt("W1"), self.f32("b1"), acts["h1"], act=2,
-                 trans_b=True, a_perm=a_feistel)
-        api.gemm(acts["h1"], self.wt("W2"), self.f32("b2"), acts["h2"], act=2, trans_b=True)
+                 trans_b=True, a_perm=a_feistel, resident=res)
+        api.gemm(acts["h1"], self.wt("W2"), self.f32("b2"), acts["h2"], act=2,
+                 trans_b=True, resident=res)
         api.gemm(acts["h2"], self.wt("W3"), self.f32("b3"), acts["head"], act=0, trans_b=True)
         return acts["head"]
 
@@ -199,8 +210,11 @@ class ActorCriticMLP:
         tiny head GEMM inside the env kernel (h2 @ W3 + b3 per env row),
         removing one launch from the latency-bound per-step chain; in the
         update, head_loss_backward computes the head from h2 itself."""
-        api.gemm(obs_bf16, self.wt("W1"), self.f32("b1"), acts["h1"], act=2, trans_b=True)
-        api.gemm(acts["h1"], self.wt("W2"), self.f32("b2"), acts["h2"], act=2, trans_b=True)
+        res = self._resident(acts["h1"].shape[0])
+        api.gemm(obs_bf16, self.wt("W1"), self.f32("b1"), acts["h1"], act=2,
+                 trans_b=True, resident=res)
+        api.gemm(acts["h1"], self.wt("W2"), self.f32("b2"), acts["h2"], act=2,
+                 trans_b=True, resident=res)
         return acts["h2"]
 
     # -- head forward + loss backward + head-layer backward ---------------
@@ -263,7 +277,7 @@ class ActorCriticMLP:
         api.wgrad(acts["h1"], dh2, self.grad("W2"), self.grad("b2"),
                   workspace=(dw_p, db_p), slabs=slabs, reduce=red)
         api.gemm(dh2, self.w("W2"), None, dh1, Yact=acts["h1"], trans_b=True,
-                 act=1, dact_tanh=True)
+                 act=1, dact_tanh=True, resident=self._resident(dh2.shape[0]))
         # layer 1
         dw_p, db_p, slabs = self._wg_workspace("W1", self.obs_dim, self.hidden, True)
         api.wgrad(obs_bf16, dh1, self.grad("W1"), self.grad("b1"),

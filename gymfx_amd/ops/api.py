@@ -51,11 +51,22 @@ def gemm(
     dact_tanh: bool = False,
     accum: bool = False,
     a_perm: "Optional[dict]" = None,
+    resident: bool = False,
 ) -> torch.Tensor:
     """a_perm (gather+first-GEMM fusion): dict(seed, minibatches, ctr_off,
     step_base, mb_ctr) — A rows are read through the epoch Feistel
-    permutation; A is the FULL rollout slab and C has minibatch rows."""
+    permutation; A is the FULL rollout slab and C has minibatch rows.
+    resident: run the weight-resident tall kernel (N=256, K<=264, trans_b,
+    bias+tanh or tanh' epilogue) when its predicate accepts the call —
+    bitwise the same result; any other call takes the usual kernel."""
     if _use_native(A):
+        if resident and a_perm is None:
+            ext = native.require()
+            N = B.shape[0] if trans_b else B.shape[1]
+            if ext.gemm_resident_ok(A.shape[0], N, A.shape[1], trans_b, act,
+                                    dact_tanh, bias is not None, accum):
+                ext.gemm_resident(A, B, bias, C, Yact, act, dact_tanh)
+                return C
         if a_perm is not None:
             native.require().gemm(A, B, bias, C, Yact, trans_b, act,
                                   dact_tanh, accum,

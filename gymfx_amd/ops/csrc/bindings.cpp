@@ -25,6 +25,9 @@ void launch_gemm(const void* A, const void* B, const float* bias, void* C,
                  const void* Yact, int M, int N, int K, bool trans_b, int act,
                  bool dact_tanh, bool add_bias, bool accum, hipStream_t stream,
                  const FeistelMap* fmp = nullptr);
+void launch_gemm_resident(const void* A, const void* Wt, const float* bias,
+                          void* C, const void* Yact, int M, int K, int act,
+                          bool dact_tanh, int max_blocks, hipStream_t stream);
 void launch_lstm_cell_fwd(const void* gates_pre, const void* gates_h,
                           const float* c_prev, float* c_new, void* h_new,
                           const bool* done, void* h_masked, float* c_masked,
@@ -601,6 +604,54 @@ void gemm_op(torch::Tensor A, torch::Tensor B, c10::optional<torch::Tensor> bias
   gymfx::launch_gemm(A.data_ptr(), B.data_ptr(), bias_p, C.data_ptr(), y_p, M,
                      N, K, trans_b, (int)act, dact_tanh, bias_p != nullptr,
                      accum, cur_stream());
+}
+
+// Weight-resident tall GEMM: C[M,256] = epilogue(A[M,K] @ Wt[256,K]^T),
+// bitwise the gemm() result for the same operands.  act=2 with bias is the
+// forward epilogue, act=1 with dact_tanh the dgrad one; anything else (see
+// gemm_resident_ok) raises.
+void gemm_resident_op(torch::Tensor A, torch::Tensor Wt,
+                      c10::optional<torch::Tensor> bias, torch::Tensor C,
+                      c10::optional<torch::Tensor> Yact, int64_t act,
+                      bool dact_tanh, int64_t max_blocks) {
+  check_bf16(A, "A");
+  check_bf16(Wt, "Wt");
+  check_bf16(C, "C");
+  TORCH_CHECK(A.dim() == 2 && Wt.dim() == 2 && C.dim() == 2,
+              "gemm_resident operands must be 2-d");
+  const int64_t M = A.size(0), K = A.size(1), N = Wt.size(0);
+  TORCH_CHECK(Wt.size(1) == K, "gemm_resident K mismatch");
+  TORCH_CHECK(C.size(0) == M && C.size(1) == N, "gemm_resident C shape");
+  TORCH_CHECK(gymfx::gemm_resident_ok(M, N, K, true, (int)act, dact_tanh,
+                                      bias.has_value(), false),
+              "gemm_resident: shape/epilogue not supported (M=", M, " N=", N,
+              " K=", K, " act=", act, " dact_tanh=", dact_tanh, ")");
+  TORCH_CHECK(max_blocks >= 0, "max_blocks must be >= 0");
+  // rows are moved in 8-byte pieces, the bias in 16-byte ones
+  auto aligned = [](const torch::Tensor& t, uintptr_t a) {
+    return reinterpret_cast<uintptr_t>(t.data_ptr()) % a == 0;
+  };
+  TORCH_CHECK(aligned(A, 8) && aligned(Wt, 8) && aligned(C, 8),
+              "gemm_resident operands must be 8-byte aligned");
+  const float* bias_p = nullptr;
+  if (bias.has_value()) {
+    check_f32(*bias, "bias");
+    TORCH_CHECK(bias->numel() == N, "bias numel");
+    TORCH_CHECK(aligned(*bias, 16), "gemm_resident bias must be 16-byte aligned");
+    bias_p = bias->data_ptr<float>();
+  }
+  const void* y_p = nullptr;
+  if (dact_tanh) {
+    TORCH_CHECK(Yact.has_value(), "dact_tanh needs Yact");
+    check_bf16(*Yact, "Yact");
+    TORCH_CHECK(Yact->dim() == 2 && Yact->size(0) == M && Yact->size(1) == N,
+                "gemm_resident Yact shape");
+    TORCH_CHECK(aligned(*Yact, 8), "gemm_resident Yact must be 8-byte aligned");
+    y_p = Yact->data_ptr();
+  }
+  gymfx::launch_gemm_resident(A.data_ptr(), Wt.data_ptr(), bias_p,
+                              C.data_ptr(), y_p, (int)M, (int)K, (int)act,
+                              dact_tanh, (int)max_blocks, cur_stream());
 }
 
 void lstm_cell_fwd_op(torch::Tensor gates_pre,
@@ -1307,6 +1358,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ap_minibatches") = 1, py::arg("ap_ctr_off") = 0,
         py::arg("ap_step_base") = py::none(),
         py::arg("ap_mb_ctr") = py::none());
+  m.def("gemm_resident", &gemm_resident_op,
+        "weight-resident tall GEMM, N=256, K<=264: C = tanh(A @ Wt^T + bias) "
+        "(act=2) or (A @ Wt^T) * (1-Yact^2) (act=1, dact_tanh); bitwise the "
+        "gemm() result; max_blocks caps the grid (0 = one workgroup per CU)",
+        py::arg("A"), py::arg("Wt"), py::arg("bias"), py::arg("C"),
+        py::arg("Yact") = py::none(), py::arg("act") = 2,
+        py::arg("dact_tanh") = false, py::arg("max_blocks") = 0);
+  m.def("gemm_resident_ok", &gymfx::gemm_resident_ok,
+        "host predicate: can gemm_resident run this shape and epilogue",
+        py::arg("M"), py::arg("N"), py::arg("K"), py::arg("trans_b") = true,
+        py::arg("act") = 2, py::arg("dact_tanh") = false,
+        py::arg("add_bias") = true, py::arg("accum") = false,
+        py::arg("a_perm") = false);
   m.def("lstm_cell_fwd", &lstm_cell_fwd_op, py::arg("gates_pre"),
         py::arg("gates_h"), py::arg("c_prev"), py::arg("c_new"),
         py::arg("h_new"), py::arg("done") = py::none(),

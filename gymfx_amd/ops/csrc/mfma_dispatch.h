@@ -174,6 +174,36 @@ inline bool gemm_instantiated(const GemmSel& s) {
   return false;
 }
 
+// Weight-resident tall GEMM (gemm_resident_kernel): a separate entry point
+// beside select_gemm, which it never changes.  The whole [256, K] weight
+// matrix sits in one LDS image per workgroup.
+constexpr int RESIDENT_N = 256;      // output columns, exactly
+constexpr int RESIDENT_LD = 264;     // LDS row stride in elements = max K
+constexpr int RESIDENT_GROUP = 256;  // rows of A per workgroup iteration
+
+// Structural only: the shape and epilogue the kernel implements.  Any M >= 1
+// is accepted (the kernel guards a ragged last group).  K % 4 == 0 because
+// rows are read in 8-byte pieces.  Whether the kernel is FASTER at a given M
+// is the caller's call (ActorCriticMLP.resident_min_rows).
+inline bool gemm_resident_ok(int64_t M, int64_t N, int64_t K, bool trans_b,
+                             int act, bool dact_tanh, bool add_bias,
+                             bool accum, bool a_perm = false) {
+  if (M < 1 || M > INT32_MAX - RESIDENT_GROUP) return false;
+  if (N != RESIDENT_N || K < 4 || K > RESIDENT_LD || K % 4 != 0) return false;
+  if (!trans_b || accum || a_perm) return false;
+  const bool fwd = act == 2 && add_bias && !dact_tanh;   // bias + tanh
+  const bool dgrad = act == 1 && dact_tanh && !add_bias;  // x (1 - y^2)
+  return fwd || dgrad;
+}
+
+// workgroups: one per 256-row group up to the CU count (or the caller's cap)
+inline int gemm_resident_grid(int64_t M, int n_cus, int max_blocks) {
+  const int64_t groups = (M + RESIDENT_GROUP - 1) / RESIDENT_GROUP;
+  int64_t cap = max_blocks > 0 ? max_blocks : n_cus;
+  if (cap < 1) cap = 1;
+  return (int)(groups < cap ? groups : cap);
+}
+
 // wgrad_glds_kernel / wgrad_partial_kernel <DB, FK, FN, PERM> on (gx,gy,gz)
 struct WgradSel {
   bool glds;

@@ -46,6 +46,14 @@ GFX_DEV float fast_tanh(float x) {
   return 1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f);
 }
 
+// The two update-phase GEMM epilogues, shared by gemm_kernel and
+// gemm_resident_kernel so both contract the same way (bitwise equal bf16).
+GFX_DEV float epi_bias_tanh(float v, float b) { return fast_tanh(v + b); }
+GFX_DEV float epi_dtanh(float v, __bf16 yact) {
+  const float y = bf2f(yact);
+  return v * (1.f - y * y);
+}
+
 GFX_DEV uint32_t feistel_encrypt_once(uint32_t x, int half, uint32_t mask,
                                       uint64_t key) {
   uint32_t a = x & mask;        // low half
@@ -327,18 +335,233 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(
         const int grow = bm + wr * 32 + mi * 16 + crow_base + r;
         if (grow >= M) continue;
         float v = acc[mi][ni][r];
-        if (ADD_BIAS) v += bias[gcol];
-        if (ACT == 2) v = fast_tanh(v);
-        if (DACT_TANH) {
-          float y = bf2f(Yact[(int64_t)grow * N + gcol]);
-          v *= (1.f - y * y);
+        if (ADD_BIAS && ACT == 2) {
+          v = epi_bias_tanh(v, bias[gcol]);
+        } else {
+          if (ADD_BIAS) v += bias[gcol];
+          if (ACT == 2) v = fast_tanh(v);
         }
+        if (DACT_TANH) v = epi_dtanh(v, Yact[(int64_t)grow * N + gcol]);
         if (ACT == 0) {
           float* cp = reinterpret_cast<float*>(C) + (int64_t)grow * N + gcol;
           *cp = ACCUM ? (*cp + v) : v;
         } else {
           reinterpret_cast<__bf16*>(C)[(int64_t)grow * N + gcol] = f2bf(v);
         }
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Weight-resident tall GEMM: C[M,256] = epilogue(A[M,K] @ Wt[256,K]^T) for
+// the update-phase layers (N = 256, K <= 264, M huge).  The whole weight
+// matrix sits in ONE LDS image per workgroup (256 rows x 264-element stride
+// = 135,168 B, K zero-padded to a multiple of 8), filled once; the
+// workgroup then loops over 256-row groups of A with no barrier.  Each of
+// the 8 waves owns 32 rows x 256 columns (128 f32 accumulators per lane),
+// loads its A fragments straight from global into registers (every byte of
+// A read exactly once) and reads the weight fragments from the image.
+// gemm_kernel stages A 4x and the weights M/64 times for the same shape.
+//
+// Bitwise equal to gemm_kernel: same MFMA, same sequential 32-deep k chunks
+// into one accumulator per output element, same zero-filled tail chunk, same
+// epilogue helpers.  The MFMA runs TRANSPOSED (weights as the A operand,
+// activations as B): a lane then holds 4 consecutive output COLUMNS of one
+// row, so the epilogue moves 8-byte bf16x4 / 16-byte bias vectors instead
+// of 2-byte scalars.  An output element depends only on its products, their
+// k positions and the accumulator, not on which operand carried which.
+//
+// EPI 0: bias + tanh -> bf16 (act=2, forward)
+// EPI 1: x (1 - Yact^2) -> bf16 (act=1 + dact_tanh, dgrad)
+// NFULL_CT: number of full 32-deep k chunks when known at compile time (8 =
+// the two workload shapes K=256/260: all A chunks of a pass are issued up
+// front), -1 = runtime loop with a one-chunk prefetch (any K % 4 == 0).
+// TAIL_CT: with NFULL_CT >= 0, whether K has a partial last chunk (behind a
+// runtime test the compiler sinks the tail loads below all the MFMAs).
+// ---------------------------------------------------------------------------
+template <int EPI, int NFULL_CT, bool TAIL_CT = false>
+__global__ __launch_bounds__(512) void gemm_resident_kernel(
+    const __bf16* __restrict__ A, const __bf16* __restrict__ Wt,
+    const float* __restrict__ bias, __bf16* __restrict__ C,
+    const __bf16* __restrict__ Yact, int M, int K) {
+  constexpr int N = RESIDENT_N, LD = RESIDENT_LD, GROUP = RESIDENT_GROUP;
+  // ONE array: the weight image, then the 256 f32 biases (an epilogue that
+  // loads them from global waits on vmcnt, i.e. on its own earlier stores)
+  __shared__ __align__(16) __bf16 Ws[N * LD + 2 * N];
+  float* bias_s = reinterpret_cast<float*>(&Ws[N * LD]);
+
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6;
+  const int lane = tid & 63;
+  const int row_l = lane & 15;
+  const int kseg = lane >> 4;  // 0..3 -> k-base = kseg*8
+
+  const int nfull = NFULL_CT >= 0 ? NFULL_CT : K / 32;
+  // 0..28, multiple of 4 (a compile-time flag in the unrolled kernels)
+  const int ktail = NFULL_CT >= 0 ? (int)TAIL_CT : K - nfull * 32;
+  const int kpad8 = (K + 7) & ~7;
+
+  // tail chunk (k >= nfull*32): each lane's 8 elements as two 8-byte halves,
+  // out-of-range halves read the row start and are selected to zero
+  const int kt = nfull * 32 + kseg * 8;
+  const bool t_lo = kt + 4 <= K, t_hi = kt + 8 <= K;
+  const int t_lo_off = t_lo ? kt : 0, t_hi_off = t_hi ? kt + 4 : 0;
+  const bool w_tv = kt < kpad8;  // weight image holds zeros in [K, kpad8)
+  const int w_t_off = w_tv ? kt : 0;
+
+  const __bf16* pa[2];
+  auto set_rows = [&](int g) {
+    for (int mi = 0; mi < 2; ++mi) {
+      const int r = min(g * GROUP + wave * 32 + mi * 16 + row_l, M - 1);
+      pa[mi] = A + (int64_t)r * K;
+    }
+  };
+  auto load_full = [&](int mi, int kc) {
+    return *reinterpret_cast<const bf16x8*>(pa[mi] + kc * 32 + kseg * 8);
+  };
+  auto load_tail = [&](int mi) {
+    bf16x4 lo = *reinterpret_cast<const bf16x4*>(pa[mi] + t_lo_off);
+    bf16x4 hi = *reinterpret_cast<const bf16x4*>(pa[mi] + t_hi_off);
+    if (!t_lo) lo = bf16x4{};
+    if (!t_hi) hi = bf16x4{};
+    return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+  };
+
+  constexpr int LATE = (NFULL_CT >= 4 && TAIL_CT) ? 2 : 0;
+  constexpr int NA = NFULL_CT >= 0 ? (NFULL_CT > 0 ? NFULL_CT : 1) : 1;
+  bf16x8 a[NA][2];
+  bf16x8 atail[2];
+  auto load_group = [&](int g) {
+    set_rows(g);
+    if (NFULL_CT >= 0) {
+      // with a tail the last LATE full chunks and the tail are issued as
+      // the first chunks are consumed: 9 chunks live at once spill
+      for (int kc = 0; kc < NFULL_CT - LATE; ++kc)
+        for (int mi = 0; mi < 2; ++mi) a[kc][mi] = load_full(mi, kc);
+    } else if (nfull > 0) {
+      for (int mi = 0; mi < 2; ++mi) a[0][mi] = load_full(mi, 0);
+    }
+    // unconditional (a branch around a load costs a vmcnt(0)): with no tail
+    // both halves read the row start and are selected to zero.  The unrolled
+    // kernel issues these after its first chunk instead, when registers free.
+    if (NFULL_CT < 0)
+      for (int mi = 0; mi < 2; ++mi) atail[mi] = load_tail(mi);
+  };
+
+  // the first group's A loads fly under the weight fill
+  load_group(blockIdx.x);
+
+  {
+    // All loads of the fill are issued before the first LDS write: a
+    // load -> wait -> write loop is 17 serial round trips to L2 (12 us of
+    // fixed cost, measured).  Out-of-range pieces re-read the last one and
+    // are not written.
+    constexpr int FILL_IT = (N * (LD / 8) + 511) / 512;
+    // 16-byte pieces per weight row (a constant in the unrolled kernels)
+    const int gpr = NFULL_CT >= 0 ? NFULL_CT * 4 + (TAIL_CT ? 1 : 0) : kpad8 / 8;
+    const int total = N * gpr;
+    bf16x4 flo[FILL_IT], fhi[FILL_IT];
+    for (int j = 0; j < FILL_IT; ++j) {
+      const int e = min(tid + j * 512, total - 1);
+      const int n = e / gpr;
+      const int k = (e - n * gpr) * 8;
+      const __bf16* src = Wt + (int64_t)n * K + k;
+      const bool hv = k + 8 <= K;  // k + 4 <= K always holds (K % 4 == 0)
+      flo[j] = *reinterpret_cast<const bf16x4*>(src);
+      fhi[j] = *reinterpret_cast<const bf16x4*>(src + (hv ? 4 : 0));
+    }
+    for (int j = 0; j < FILL_IT; ++j) {
+      const int e = tid + j * 512;
+      const int n = e / gpr;
+      const int k = (e - n * gpr) * 8;
+      if (e < total) {
+        const bf16x4 hi = k + 8 <= K ? fhi[j] : bf16x4{};
+        *reinterpret_cast<bf16x8*>(&Ws[n * LD + k]) =
+            __builtin_shufflevector(flo[j], hi, 0, 1, 2, 3, 4, 5, 6, 7);
+      }
+    }
+    if (EPI == 0 && tid < N) bias_s[tid] = bias[tid];
+  }
+  __syncthreads();
+
+  const __bf16* wrow = &Ws[row_l * LD + kseg * 8];
+  f32x4 acc[2][16];
+  auto mma_chunk = [&](int k0, const bf16x8& a0, const bf16x8& a1) {
+    for (int ni = 0; ni < 16; ++ni) {
+      // fence the scheduler every 4 fragments: left alone it hoists the
+      // weight reads of all chunks above the MFMAs and spills 2 KB per lane
+      if (ni % 4 == 0) __builtin_amdgcn_sched_barrier(0);
+      const bf16x8 wf =
+          *reinterpret_cast<const bf16x8*>(wrow + ni * 16 * LD + k0);
+      acc[0][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, a0, acc[0][ni],
+                                                           0, 0, 0);
+      acc[1][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, a1, acc[1][ni],
+                                                           0, 0, 0);
+    }
+  };
+
+  for (int g = blockIdx.x; g * GROUP < M; g += gridDim.x) {
+    if (g != (int)blockIdx.x) load_group(g);
+    for (int mi = 0; mi < 2; ++mi)
+      for (int ni = 0; ni < 16; ++ni) acc[mi][ni] = f32x4{};
+
+    if (NFULL_CT >= 0) {
+      for (int kc = 0; kc < NFULL_CT; ++kc) {
+        const int slot = kc >= NFULL_CT - LATE ? kc - (NFULL_CT - LATE) : kc;
+        mma_chunk(kc * 32, a[slot][0], a[slot][1]);
+        if (kc < LATE)  // chunk kc's registers are free again
+          for (int mi = 0; mi < 2; ++mi)
+            a[kc][mi] = load_full(mi, NFULL_CT - LATE + kc);
+        if (TAIL_CT && kc == LATE)
+          for (int mi = 0; mi < 2; ++mi) atail[mi] = load_tail(mi);
+      }
+    } else {
+      for (int kc = 0; kc < nfull; ++kc) {
+        // unconditional prefetch (the last one re-reads its own chunk): a
+        // branch around the loads would cost a full vmcnt(0) per iteration
+        const int kn = min(kc + 1, nfull - 1);
+        const bf16x8 n0 = load_full(0, kn), n1 = load_full(1, kn);
+        mma_chunk(kc * 32, a[0][0], a[0][1]);
+        a[0][0] = n0;
+        a[0][1] = n1;
+      }
+    }
+    if (ktail) {
+      for (int ni = 0; ni < 16; ++ni) {
+        bf16x8 wf = *reinterpret_cast<const bf16x8*>(
+            &Ws[(ni * 16 + row_l) * LD + w_t_off]);
+        if (!w_tv) wf = bf16x8{};
+        acc[0][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            wf, atail[0], acc[0][ni], 0, 0, 0);
+        acc[1][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            wf, atail[1], acc[1][ni], 0, 0, 0);
+      }
+    }
+
+    // transposed C/D map: lane l, reg r -> row = l&15, col = (l>>4)*4 + r
+    for (int mi = 0; mi < 2; ++mi) {
+      const int grow = g * GROUP + wave * 32 + mi * 16 + row_l;
+      if (grow >= M) continue;
+      const int64_t o = (int64_t)grow * N + kseg * 4;
+      // all of a row's Yact pieces in flight before the first store: loads
+      // and stores share vmcnt, one load per store would serialize them
+      bf16x4 y[16];
+      if (EPI == 1)
+        for (int ni = 0; ni < 16; ++ni)
+          y[ni] = *reinterpret_cast<const bf16x4*>(&Yact[o + ni * 16]);
+      for (int ni = 0; ni < 16; ++ni) {
+        bf16x4 out;
+        if (EPI == 0) {
+          const f32x4 b =
+              *reinterpret_cast<const f32x4*>(&bias_s[ni * 16 + kseg * 4]);
+          for (int r = 0; r < 4; ++r)
+            out[r] = f2bf(epi_bias_tanh(acc[mi][ni][r], b[r]));
+        } else {
+          for (int r = 0; r < 4; ++r)
+            out[r] = f2bf(epi_dtanh(acc[mi][ni][r], y[ni][r]));
+        }
+        *reinterpret_cast<bf16x4*>(&C[o + ni * 16]) = out;
       }
     }
   }
@@ -2614,6 +2837,44 @@ void launch_gemm(const void* A, const void* B, const float* bias, void* C,
   // forward epilogue): unreachable by construction, abort loudly if it
   // ever is
   abort();
+}
+
+// Weight-resident tall GEMM (gemm_resident_kernel).  The caller has checked
+// gemm_resident_ok; act/dact_tanh pick the epilogue.  max_blocks caps the
+// grid (0 = one workgroup per CU, at most one per 256-row group).
+void launch_gemm_resident(const void* A, const void* Wt, const float* bias,
+                          void* C, const void* Yact, int M, int K, int act,
+                          bool dact_tanh, int max_blocks, hipStream_t stream) {
+  if (!gemm_resident_ok(M, RESIDENT_N, K, true, act, dact_tanh,
+                        bias != nullptr, false))
+    abort();
+  static const int n_cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount,
+                              dev) != hipSuccess)
+      return 256;
+    return n;
+  }();
+  const dim3 grid(gemm_resident_grid(M, n_cus, max_blocks)), block(512);
+  const __bf16* a = reinterpret_cast<const __bf16*>(A);
+  const __bf16* w = reinterpret_cast<const __bf16*>(Wt);
+  const __bf16* y = reinterpret_cast<const __bf16*>(Yact);
+  __bf16* c = reinterpret_cast<__bf16*>(C);
+#define RESIDENT(EPI, NF, TAIL)                                               \
+  hipLaunchKernelGGL((gemm_resident_kernel<EPI, NF, TAIL>), grid, block, 0,   \
+                     stream, a, w, bias, c, y, M, K)
+#define RESIDENT_EPI(EPI)                                                     \
+  do {                                                                        \
+    if (K == 256) RESIDENT(EPI, 8, false);                                    \
+    else if (K > 256) RESIDENT(EPI, 8, true);                                 \
+    else RESIDENT(EPI, -1, false);                                            \
+  } while (0)
+  // K = 256..264 (the workload's layers) have 8 full chunks: unrolled kernel
+  if (dact_tanh) RESIDENT_EPI(1);
+  else RESIDENT_EPI(0);
+#undef RESIDENT_EPI
+#undef RESIDENT
 }
 
 void launch_slab_reduce(const float* dW_part, const float* db_part, float* dW,
