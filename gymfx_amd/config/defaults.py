@@ -72,6 +72,13 @@ DEFAULT_VALUES = {
     "financing_rate_data_file": None,  # or a CSV path with the same columns
     "rollover_hour_utc": 22,
     "enforce_margin_preflight": False,  # deny fills lacking free margin
+    # seeded probabilistic fill model (off at 1 / 1 / 0; an
+    # execution_cost_profile, when given, is authoritative for all five)
+    "prob_fill_on_limit": 1.0,   # chance per bar that a touched take-profit fills
+    "prob_fill_on_stop": 1.0,    # chance per bar that a touched stop fills
+    "prob_slippage": 0.0,        # chance that a market fill slips by fill_slip_rate
+    "fill_slip_rate": 0.0,       # extra adverse rate of a slipped market fill
+    "fill_random_seed": 0,       # keys the stateless per-(env, bar) draws
 
     # PPO training (mode=training; BASELINE configs #2-#4)
     "policy_model": "mlp",       # mlp | lstm (recurrent PPO)

@@ -47,6 +47,11 @@ class ExecutionCostProfile:
     margin_model: str
     enforce_margin_preflight: bool
     random_seed: int
+    # optional seeded fill model (defaults: every touched order fills, no
+    # extra slippage); random_seed keys the draws
+    prob_fill_on_limit: float = 1.0
+    prob_fill_on_stop: float = 1.0
+    prob_slippage: float = 0.0
 
     @property
     def slippage_rate_per_side(self) -> Decimal:
@@ -104,6 +109,9 @@ class ExecutionCostProfile:
             margin_model=str(raw["margin_model"]),
             enforce_margin_preflight=bool(raw["enforce_margin_preflight"]),
             random_seed=int(raw["random_seed"]),
+            prob_fill_on_limit=float(raw.get("prob_fill_on_limit", 1.0)),
+            prob_fill_on_stop=float(raw.get("prob_fill_on_stop", 1.0)),
+            prob_slippage=float(raw.get("prob_slippage", 0.0)),
         )
         for field in ("commission_rate_per_side", "full_spread_rate", "slippage_bps_per_side"):
             if getattr(profile, field) < 0:
@@ -118,6 +126,9 @@ class ExecutionCostProfile:
             raise ValueError("unsupported limit_fill_policy")
         if profile.margin_model not in _MARGIN_MODELS:
             raise ValueError("unsupported margin_model")
+        for field in ("prob_fill_on_limit", "prob_fill_on_stop", "prob_slippage"):
+            if not 0.0 <= getattr(profile, field) <= 1.0:
+                raise ValueError(f"{field} must lie in [0, 1]")
         return profile
 
 

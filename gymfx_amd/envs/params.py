@@ -55,6 +55,19 @@ RISK_MODES = {
 }
 
 
+# fill-model draws are 53-bit integers compared against int(p * 2**53)
+FILL_DRAW_RANGE = 1 << 53
+
+
+def fill_threshold(prob: float, name: str) -> int:
+    """Integer threshold of a fill-model probability; u53 < threshold fires,
+    so 1 always fires and 0 never does."""
+    prob = float(prob)
+    if not 0.0 <= prob <= 1.0:  # also rejects NaN
+        raise ValueError(f"{name} must lie in [0, 1]; got {prob!r}")
+    return int(prob * FILL_DRAW_RANGE)
+
+
 def _f(config: Dict[str, Any], key: str, default: float) -> float:
     v = config.get(key, default)
     return default if v is None else float(v)
@@ -155,6 +168,17 @@ class EnvParams:
     latency_bars: int = 0                # floor(latency_ms / bar duration)
     margin_model: int = 0                # 0 leveraged, 1 standard
     margin_init_rate: float = 0.03       # used by margin_model=standard
+    # seeded probabilistic fill model (off at the 1 / 1 / 0 defaults)
+    prob_fill_on_limit: float = 1.0
+    prob_fill_on_stop: float = 1.0
+    prob_slippage: float = 0.0
+    fill_slip_rate: float = 0.0          # extra adverse rate when a fill slips
+    fill_random_seed: int = 0
+    # integer draw thresholds int(p * 2**53) (set_fill_model)
+    fill_thr_limit: int = FILL_DRAW_RANGE
+    fill_thr_stop: int = FILL_DRAW_RANGE
+    fill_thr_slip: int = 0
+    fill_model_on: bool = False
     # event-context overlay
     event_context_execution_overlay: bool = False
     event_context_no_trade_column: str = "event_no_trade_window_active"
@@ -277,6 +301,11 @@ class EnvParams:
             str(config.get("margin_model", "leveraged"))]
         p.margin_init_rate = _f(config, "margin_init_rate", 0.03)
         latency_ms = _f(config, "latency_ms", 0.0)
+        p.prob_fill_on_limit = _f(config, "prob_fill_on_limit", 1.0)
+        p.prob_fill_on_stop = _f(config, "prob_fill_on_stop", 1.0)
+        p.prob_slippage = _f(config, "prob_slippage", 0.0)
+        p.fill_slip_rate = _f(config, "fill_slip_rate", 0.0)
+        p.fill_random_seed = _i(config, "fill_random_seed", 0)
         p.rollover_hour_utc = int(config.get("rollover_hour_utc", 22) or 22)
         p.stage_b_force_close_obs = _b(config, "stage_b_force_close_obs", False)
         p.force_close_window_hours = _i(config, "force_close_window_hours", 4)
@@ -335,6 +364,15 @@ class EnvParams:
             p.limit_fill_policy = _LIMIT_POLICIES[prof.limit_fill_policy]
             p.margin_model = _MARGIN_MODELS[prof.margin_model]
             latency_ms = float(prof.latency_ms)
+            # ... and for the fill model: probabilities, seed and the extra
+            # slip a slipped market fill pays
+            p.prob_fill_on_limit = prof.prob_fill_on_limit
+            p.prob_fill_on_stop = prof.prob_fill_on_stop
+            p.prob_slippage = prof.prob_slippage
+            p.fill_slip_rate = f["slippage_rate_per_side"]
+            p.fill_random_seed = prof.random_seed
+
+        p.set_fill_model()
 
         # sub-bar latency collapses to next-open at OHLC granularity;
         # each full bar duration of latency delays the fill one more bar
@@ -343,6 +381,18 @@ class EnvParams:
 
         p.finalize()
         return p
+
+    def set_fill_model(self) -> None:
+        """Validate the fill probabilities and derive the integer draw
+        thresholds; the model is on iff any threshold leaves its default."""
+        self.fill_thr_limit = fill_threshold(self.prob_fill_on_limit, "prob_fill_on_limit")
+        self.fill_thr_stop = fill_threshold(self.prob_fill_on_stop, "prob_fill_on_stop")
+        self.fill_thr_slip = fill_threshold(self.prob_slippage, "prob_slippage")
+        self.fill_model_on = (
+            self.fill_thr_limit != FILL_DRAW_RANGE
+            or self.fill_thr_stop != FILL_DRAW_RANGE
+            or self.fill_thr_slip != 0
+        )
 
     def finalize(self) -> None:
         """Compute the flat observation layout (block name, width)."""

@@ -39,9 +39,10 @@ from .params import (
     STRATEGY_DIRECT,
     STRATEGY_FIXED_SLTP,
 )
-from .state import ACTION_COUNTERS, EXEC_COUNTERS, EnvState
+from .state import ACTION_COUNTERS, EXEC_COUNTERS, FILL_COUNTERS, EnvState
 
 _E = {name: i for i, name in enumerate(EXEC_COUNTERS)}
+_FD = {name: i for i, name in enumerate(FILL_COUNTERS)}
 _A = {name: i for i, name in enumerate(ACTION_COUNTERS)}
 
 
@@ -95,6 +96,55 @@ def _close_position(
     st.br_armed = st.br_armed & ~mask
     if counter is not None:
         st.exec_diag[:, _E[counter]] += mask.to(torch.int32)
+
+
+# ---------------------------------------------------------------------------
+# Fill-model draws: stateless, counter-based, integer-compared.  splitmix64
+# in int64 torch arithmetic (add/multiply wrap mod 2^64; the logical right
+# shift is the arithmetic one with the sign-extension bits masked off).
+# ---------------------------------------------------------------------------
+
+def _s64(x: int) -> int:
+    """Two's-complement int64 view of an unsigned 64-bit constant."""
+    x &= 0xFFFFFFFFFFFFFFFF
+    return x - (1 << 64) if x >= (1 << 63) else x
+
+
+_SM_G = _s64(0x9E3779B97F4A7C15)
+_SM_C1 = _s64(0xBF58476D1CE4E5B9)
+_SM_C2 = _s64(0x94D049BB133111EB)
+
+FILL_CH_LIMIT, FILL_CH_STOP, FILL_CH_SLIP_CLOSE, FILL_CH_SLIP_OPEN = 0, 1, 2, 3
+
+
+def _lsr(x: torch.Tensor, k: int) -> torch.Tensor:
+    return (x >> k) & ((1 << (64 - k)) - 1)
+
+
+def _splitmix64(x: torch.Tensor) -> torch.Tensor:
+    x = x + _SM_G
+    x = (x ^ _lsr(x, 30)) * _SM_C1
+    x = (x ^ _lsr(x, 27)) * _SM_C2
+    return x ^ _lsr(x, 31)
+
+
+def fill_key(seed: int, n: torch.Tensor, t: torch.Tensor, ch: int) -> torch.Tensor:
+    """64-bit draw key of (seed, global env index, market row, channel) as
+    int64 bit patterns: splitmix64(splitmix64(seed ^ n*G) ^ (t << 2 | ch))."""
+    n = n.to(torch.int64)
+    t = t.to(torch.int64)
+    env_key = _splitmix64((n * _SM_G) ^ _s64(seed))
+    return _splitmix64(env_key ^ ((t << 2) | ch))
+
+
+def fill_u53(seed: int, n: torch.Tensor, t: torch.Tensor, ch: int) -> torch.Tensor:
+    """The 53-bit draw (top bits of the key), a non-negative int64."""
+    return _lsr(fill_key(seed, n, t, ch), 11)
+
+
+def _fill_fires(params: EnvParams, n: torch.Tensor, t: torch.Tensor, ch: int,
+                thr: int) -> torch.Tensor:
+    return fill_u53(params.fill_random_seed, n, t, ch) < thr
 
 
 def _buy_fill(open_px: torch.Tensor, slip: float) -> torch.Tensor:
@@ -186,14 +236,38 @@ def step_torch(
     st.pend_wait = torch.where(in_transit, st.pend_wait - 1, st.pend_wait)
     deliver = ~in_transit
 
+    # fill model: a delivered market order slips by an extra fill_slip_rate
+    # with probability prob_slippage; the effective rate is formed in f32
+    # (f32(slip) + f32(rate)), op-for-op the kernel.  The close and the
+    # open of a flip draw on their own channels.
+    fm = params.fill_model_on
+    if fm:
+        env_n = torch.arange(N, dtype=torch.int64, device=device)
+        slip32 = torch.full((N,), slip, dtype=torch.float32, device=device)
+        rate32 = torch.full((N,), params.fill_slip_rate, dtype=torch.float32,
+                            device=device)
+
     close_m = valid & deliver & st.pend_close & (st.pos != 0)
     exit_buy = st.pos < 0
-    close_fill = torch.where(exit_buy, _buy_fill(o_px, slip), _sell_fill(o_px, slip))
+    close_slip = slip
+    if fm:
+        slips_c = _fill_fires(params, env_n, t, FILL_CH_SLIP_CLOSE,
+                              params.fill_thr_slip)
+        close_slip = torch.where(slips_c, slip32 + rate32, slip32)
+        st.fill_diag[:, _FD["market_fill_slips"]] += (close_m & slips_c).to(torch.int32)
+    close_fill = torch.where(exit_buy, _buy_fill(o_px, close_slip),
+                             _sell_fill(o_px, close_slip))
     _close_position(st, close_m, close_fill, params)
 
     open_m = valid & deliver & (st.pend_open_dir != 0) & (st.pos == 0)
     odir = st.pend_open_dir.to(torch.float32)
-    open_fill = torch.where(odir > 0, _buy_fill(o_px, slip), _sell_fill(o_px, slip))
+    open_slip = slip
+    if fm:
+        slips_o = _fill_fires(params, env_n, t, FILL_CH_SLIP_OPEN,
+                              params.fill_thr_slip)
+        open_slip = torch.where(slips_o, slip32 + rate32, slip32)
+    open_fill = torch.where(odir > 0, _buy_fill(o_px, open_slip),
+                            _sell_fill(o_px, open_slip))
     if bool(open_m.any()):
         size = st.pend_open_size.to(torch.float64)
         fill64 = open_fill.to(torch.float64)
@@ -211,6 +285,8 @@ def step_torch(
             denied = open_m & (st.cash < margin + comm)
             st.exec_diag[:, _E["margin_preflight_denied"]] += denied.to(torch.int32)
             open_m = open_m & ~denied
+        if fm:  # a preflight-denied open did not fill, so it cannot slip
+            st.fill_diag[:, _FD["market_fill_slips"]] += (open_m & slips_o).to(torch.int32)
         st.cash = torch.where(open_m, st.cash - margin - comm, st.cash)
         st.margin_used = torch.where(open_m, margin, st.margin_used)
         st.commission_paid = torch.where(open_m, st.commission_paid + comm, st.commission_paid)
@@ -242,24 +318,53 @@ def step_torch(
         is_long = st.pos > 0
         lim = params.limit_fill_policy
 
-        def tp_ge(px):  # long take-profit trigger at px
+        def tp_ge_raw(px):  # long take-profit trigger at px
             return px >= st.br_tp if lim == 0 else px > st.br_tp
 
-        def tp_le(px):  # short take-profit trigger at px
+        def tp_le_raw(px):  # short take-profit trigger at px
             return px <= st.br_tp if lim == 0 else px < st.br_tp
+
+        # fill model: one draw per leg per bar; a leg whose draw fails is
+        # invisible to the whole walk on this bar (gap checks included)
+        # and is tried again on the next bar with that bar's draws
+        if fm:
+            sl_on = _fill_fires(params, env_n, t, FILL_CH_STOP, params.fill_thr_stop)
+            tp_on = _fill_fires(params, env_n, t, FILL_CH_LIMIT, params.fill_thr_limit)
+            sl_trig = torch.where(is_long, (o_px <= st.br_sl) | (l_px <= st.br_sl),
+                                  (o_px >= st.br_sl) | (h_px >= st.br_sl))
+            tp_trig = torch.where(is_long, tp_ge_raw(o_px) | tp_ge_raw(h_px),
+                                  tp_le_raw(o_px) | tp_le_raw(l_px))
+            st.fill_diag[:, _FD["bracket_sl_fill_misses"]] += (
+                chk & ~sl_on & sl_trig).to(torch.int32)
+            st.fill_diag[:, _FD["bracket_tp_fill_misses"]] += (
+                chk & ~tp_on & tp_trig).to(torch.int32)
+        else:
+            sl_on = tp_on = torch.ones_like(chk)
+
+        def tp_ge(px):
+            return tp_on & tp_ge_raw(px)
+
+        def tp_le(px):
+            return tp_on & tp_le_raw(px)
+
+        def sl_le(px):  # long stop trigger at px
+            return sl_on & (px <= st.br_sl)
+
+        def sl_ge(px):  # short stop trigger at px
+            return sl_on & (px >= st.br_sl)
 
         gap_tp_price = st.br_tp if lim == 2 else o_px
         if params.intrabar_collision_policy == 0:  # worst_case
             # long: SL below (sell stop), TP above (sell limit)
-            l_sl_gap = chk & is_long & (o_px <= st.br_sl)
-            l_sl_hit = chk & is_long & ~l_sl_gap & (l_px <= st.br_sl)
+            l_sl_gap = chk & is_long & sl_le(o_px)
+            l_sl_hit = chk & is_long & ~l_sl_gap & sl_le(l_px)
             l_tp_gap = chk & is_long & ~l_sl_gap & ~l_sl_hit & tp_ge(o_px)
             l_tp_hit = (
                 chk & is_long & ~l_sl_gap & ~l_sl_hit & ~l_tp_gap & tp_ge(h_px)
             )
             # short: SL above (buy stop), TP below (buy limit)
-            s_sl_gap = chk & ~is_long & (o_px >= st.br_sl)
-            s_sl_hit = chk & ~is_long & ~s_sl_gap & (h_px >= st.br_sl)
+            s_sl_gap = chk & ~is_long & sl_ge(o_px)
+            s_sl_hit = chk & ~is_long & ~s_sl_gap & sl_ge(h_px)
             s_tp_gap = chk & ~is_long & ~s_sl_gap & ~s_sl_hit & tp_le(o_px)
             s_tp_hit = (
                 chk & ~is_long & ~s_sl_gap & ~s_sl_hit & ~s_tp_gap & tp_le(l_px)
@@ -275,16 +380,15 @@ def step_torch(
                 low_first = c_px >= o_px  # up bar: dip printed first
             else:  # ohlc: high before low
                 low_first = torch.zeros_like(chk)
-            sl_gap = chk & torch.where(is_long, o_px <= st.br_sl,
-                                       o_px >= st.br_sl)
+            sl_gap = chk & torch.where(is_long, sl_le(o_px), sl_ge(o_px))
             tp_gap = chk & ~sl_gap & torch.where(is_long, tp_ge(o_px),
                                                  tp_le(o_px))
             rest = chk & ~sl_gap & ~tp_gap
             # per-extreme triggers (each extreme serves one leg per side)
-            low_sl = is_long & (l_px <= st.br_sl)     # long stop at low
+            low_sl = is_long & sl_le(l_px)            # long stop at low
             low_tp = ~is_long & tp_le(l_px)           # short limit at low
             high_tp = is_long & tp_ge(h_px)           # long limit at high
-            high_sl = ~is_long & (h_px >= st.br_sl)   # short stop at high
+            high_sl = ~is_long & sl_ge(h_px)          # short stop at high
             first_sl = torch.where(low_first, low_sl, high_sl)
             first_tp = torch.where(low_first, low_tp, high_tp)
             second_sl = torch.where(low_first, high_sl, low_sl)

@@ -36,6 +36,14 @@ EXEC_COUNTERS = (
     "margin_preflight_denied",
 )
 
+# fill-model counters (== ops/csrc/env_common.h FillCounter).  Kept in a
+# tensor of their own: widening exec_diag would break older checkpoints.
+FILL_COUNTERS = (
+    "bracket_sl_fill_misses",
+    "bracket_tp_fill_misses",
+    "market_fill_slips",
+)
+
 ACTION_COUNTERS = (
     "steps",
     "hold_actions",
@@ -110,6 +118,7 @@ class EnvState:
     # diagnostics
     exec_diag: torch.Tensor       # i32 [N, len(EXEC_COUNTERS)]
     act_diag: torch.Tensor        # i32 [N, len(ACTION_COUNTERS)]
+    fill_diag: torch.Tensor       # i32 [N, len(FILL_COUNTERS)]
     raw_abs_sum: torch.Tensor     # f32 [N]
     raw_min: torch.Tensor         # f32 [N]
     raw_max: torch.Tensor         # f32 [N]
@@ -179,6 +188,7 @@ def alloc_state(params: EnvParams, device: torch.device) -> EnvState:
         pip_env=torch.full((N,), params.pip_size, **f32),
         exec_diag=torch.zeros(N, len(EXEC_COUNTERS), **i32),
         act_diag=torch.zeros(N, len(ACTION_COUNTERS), **i32),
+        fill_diag=torch.zeros(N, len(FILL_COUNTERS), **i32),
         raw_abs_sum=torch.zeros(N, **f32),
         raw_min=torch.full((N,), float("inf"), **f32),
         raw_max=torch.full((N,), float("-inf"), **f32),
@@ -234,6 +244,7 @@ def reset_state_(st: EnvState, params: EnvParams, mask: torch.Tensor) -> None:
     st.episode_return[mask] = 0.0
     st.exec_diag[mask] = 0
     st.act_diag[mask] = 0
+    st.fill_diag[mask] = 0
     st.raw_abs_sum[mask] = 0.0
     st.raw_min[mask] = float("inf")
     st.raw_max[mask] = float("-inf")

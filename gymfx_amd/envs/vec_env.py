@@ -18,7 +18,8 @@ from ..data.feed import concat_markets
 from .market import MarketTensors, build_market_tensors
 from .params import EnvParams
 from .reference_step import build_obs_torch, step_torch
-from .state import ACTION_COUNTERS, EXEC_COUNTERS, EnvState, alloc_state, reset_state_
+from .state import (ACTION_COUNTERS, EXEC_COUNTERS, FILL_COUNTERS, EnvState,
+                    alloc_state, reset_state_)
 
 
 def resolve_device(spec: Any = "auto") -> torch.device:
@@ -287,6 +288,14 @@ class VecFxEnv:
         return {
             name: int(self.st.exec_diag[i, k].item())
             for k, name in enumerate(EXEC_COUNTERS)
+        }
+
+    def fill_model_diagnostics(self, i: int = 0) -> Dict[str, int]:
+        """Fill-model counters: bars on which a touched bracket leg missed
+        its fill draw, and market fills that slipped."""
+        return {
+            name: int(self.st.fill_diag[i, k].item())
+            for k, name in enumerate(FILL_COUNTERS)
         }
 
     def analyzers(self, i: int = 0) -> Dict[str, Any]:

@@ -233,6 +233,13 @@ struct GymFxEngine {
     K.feature_clip = gf("feature_clip");
     K.overlay_threshold = gf("overlay_threshold");
     K.margin_init_rate = gf("margin_init_rate");
+    // fill model: thresholds are exact integers (<= 2^53), the seed is
+    // the full unsigned 64-bit value
+    K.fill_slip_rate = gf("fill_slip_rate");
+    K.fill_seed = py::cast<uint64_t>(iparams["fill_seed"]);
+    K.fill_thr_limit = py::cast<uint64_t>(iparams["fill_thr_limit"]);
+    K.fill_thr_stop = py::cast<uint64_t>(iparams["fill_thr_stop"]);
+    K.fill_thr_slip = py::cast<uint64_t>(iparams["fill_thr_slip"]);
 
     // market pointers
     P.open_px = ptr<float>(market, "open");
@@ -302,6 +309,11 @@ struct GymFxEngine {
     P.pip_env = ptr<float>(state, "pip_env");
     P.exec_diag = ptr<int>(state, "exec_diag");
     P.act_diag = ptr<int>(state, "act_diag");
+    P.fill_diag = ptr<int>(state, "fill_diag");
+    TORCH_CHECK(state["fill_diag"].is_contiguous() &&
+                    state["fill_diag"].numel() ==
+                        (int64_t)K.n_envs * FILL_COUNTER_N,
+                "fill_diag must be contiguous i32 [n_envs, 3]");
     P.raw_abs_sum = ptr<float>(state, "raw_abs_sum");
     P.raw_min = ptr<float>(state, "raw_min");
     P.raw_max = ptr<float>(state, "raw_max");

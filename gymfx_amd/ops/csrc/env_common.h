@@ -40,6 +40,7 @@ enum Flags {
   F_AUTORESET = 1 << 14,
   F_FINANCING = 1 << 15,
   F_PREFLIGHT = 1 << 16,
+  F_FILL_MODEL = 1 << 17,
 };
 
 // execution-diagnostics counter indices (== envs/state.py EXEC_COUNTERS)
@@ -64,6 +65,17 @@ enum ExecCounter {
   E_MARGIN_PREFLIGHT_DENIED,
   EXEC_COUNTER_N,
 };
+
+// fill-model counter indices (== envs/state.py FILL_COUNTERS)
+enum FillCounter {
+  FD_BRACKET_SL_MISSES = 0,
+  FD_BRACKET_TP_MISSES,
+  FD_MARKET_SLIPS,
+  FILL_COUNTER_N,
+};
+
+// fill-model draw channels (one independent stream per order kind)
+enum FillChannel { FCH_LIMIT = 0, FCH_STOP = 1, FCH_SLIP_CLOSE = 2, FCH_SLIP_OPEN = 3 };
 
 enum ActCounter {
   A_STEPS = 0,
@@ -181,6 +193,11 @@ struct EnvParamsK {
   double fc_pen_coef, fc_pen_window_hours;
   double feature_clip, overlay_threshold;
   double margin_init_rate;
+  // seeded probabilistic fill model (F_FILL_MODEL): a draw fires when its
+  // 53-bit hash is below the host-computed threshold int(p * 2^53)
+  double fill_slip_rate;
+  unsigned long long fill_seed;
+  unsigned long long fill_thr_limit, fill_thr_stop, fill_thr_slip;
   // fused policy sampling (set per step() call when head != null)
   int head_hidden;           // h2 width for the head-in-step fusion
   int rnn_hidden;            // LSTM state width for the fused state reset
@@ -232,6 +249,7 @@ struct EnvPtrs {
   const float *pip_env;      // [N] per-env pip size
   int *exec_diag;            // [N, EXEC_COUNTER_N]
   int *act_diag;             // [N, ACT_COUNTER_N]
+  int *fill_diag;            // [N, FILL_COUNTER_N]
   float *raw_abs_sum, *raw_min, *raw_max;
   // fused policy sampling (optional; saves one kernel launch per rollout
   // step): when `head` is non-null the step kernel samples the action

@@ -20,6 +20,18 @@ namespace gymfx {
 GFX_DEV float buy_fill(float o, float slip) { return o * (1.0f + slip); }
 GFX_DEV float sell_fill(float o, float slip) { return o * (1.0f - slip); }
 
+// Fill-model draw: a pure function of (seed, global env index, absolute
+// market row, channel) — no RNG state, so graph replay, split stepping,
+// autoreset and resume need no bookkeeping.  Integer compare against the
+// host-computed threshold int(p * 2^53); mirrors reference_step._fill_fires.
+GFX_DEV bool fill_fires(const EnvParamsK& K, int n, int t, int ch,
+                        unsigned long long thr) {
+  const uint64_t env_key =
+      splitmix64(K.fill_seed ^ ((uint64_t)n * 0x9E3779B97F4A7C15ull));
+  const uint64_t key = splitmix64(env_key ^ (((uint64_t)t << 2) | (uint64_t)ch));
+  return (key >> 11) < thr;
+}
+
 // Close the full position at `fill`; mirrors reference_step._close_position.
 GFX_DEV void close_position(const EnvPtrs& P, const EnvParamsK& K, int n,
                             double fill, int counter) {
@@ -90,11 +102,15 @@ GFX_DEV void reset_env(const EnvPtrs& P, const EnvParamsK& K, int n) {
   P.episode_return[n] = 0.0;
   for (int i = 0; i < EXEC_COUNTER_N; ++i) P.exec_diag[n * EXEC_COUNTER_N + i] = 0;
   for (int i = 0; i < ACT_COUNTER_N; ++i) P.act_diag[n * ACT_COUNTER_N + i] = 0;
+  for (int i = 0; i < FILL_COUNTER_N; ++i) P.fill_diag[n * FILL_COUNTER_N + i] = 0;
   P.raw_abs_sum[n] = 0.f;
   P.raw_min[n] = INFINITY;
   P.raw_max[n] = -INFINITY;
 }
 
+// FILL selects the fill-model code at compile time (the launchers read
+// F_FILL_MODEL on the host), so the default path carries none of it.
+template <bool FILL>
 GFX_DEV void env_step_one(const EnvPtrs& P, const EnvParamsK& K, const int n,
                           const int env_lo) {
   const int T = K.T;
@@ -104,6 +120,8 @@ GFX_DEV void env_step_one(const EnvPtrs& P, const EnvParamsK& K, const int n,
   const float slip = (float)K.slippage;
   int* ediag = P.exec_diag + (int64_t)n * EXEC_COUNTER_N;
   int* adiag = P.act_diag + (int64_t)n * ACT_COUNTER_N;
+  int* fdiag = P.fill_diag + (int64_t)n * FILL_COUNTER_N;
+  constexpr bool fill_on = FILL;
 
   // ---- fused policy sampling (optional) ------------------------------
   // One thread already owns env row n; sampling here (identical math to
@@ -218,13 +236,24 @@ GFX_DEV void env_step_one(const EnvPtrs& P, const EnvParamsK& K, const int n,
   if (in_transit) {
     P.pend_wait[n] -= 1;
   } else {
+    // fill model: a delivered market order slips by an extra
+    // fill_slip_rate with probability prob_slippage (the close and the
+    // open of a flip draw on their own channels)
     if (valid && P.pend_close[n] && P.pos[n] != 0.0) {
-      float fill = (P.pos[n] < 0) ? buy_fill(o_px, slip) : sell_fill(o_px, slip);
+      float s = slip;
+      if (fill_on && fill_fires(K, n, t, FCH_SLIP_CLOSE, K.fill_thr_slip)) {
+        s = slip + (float)K.fill_slip_rate;
+        fdiag[FD_MARKET_SLIPS] += 1;
+      }
+      float fill = (P.pos[n] < 0) ? buy_fill(o_px, s) : sell_fill(o_px, s);
       close_position(P, K, n, (double)fill, -1);
     }
     if (valid && P.pend_open_dir[n] != 0 && P.pos[n] == 0.0) {
+      const bool slips =
+          fill_on && fill_fires(K, n, t, FCH_SLIP_OPEN, K.fill_thr_slip);
+      const float s = slips ? slip + (float)K.fill_slip_rate : slip;
       double dir = (double)P.pend_open_dir[n];
-      double fill = (double)(dir > 0 ? buy_fill(o_px, slip) : sell_fill(o_px, slip));
+      double fill = (double)(dir > 0 ? buy_fill(o_px, s) : sell_fill(o_px, s));
       double size = (double)P.pend_open_size[n];
       double notional = size * fill;
       double comm = notional * K.commission;
@@ -246,6 +275,7 @@ GFX_DEV void env_step_one(const EnvPtrs& P, const EnvParamsK& K, const int n,
       P.last_trade_cost[n] += comm;
       P.pos[n] = dir * size;
       P.avg_entry[n] = fill;
+      if (slips) fdiag[FD_MARKET_SLIPS] += 1;
       if (P.pend_sl[n] > 0.f || P.pend_tp[n] > 0.f) {
         P.br_active[n] = true;
         P.br_armed[n] = true;  // children active from NEXT bar
@@ -277,22 +307,40 @@ GFX_DEV void env_step_one(const EnvPtrs& P, const EnvParamsK& K, const int n,
     const int lim = K.limit_policy;
     float trig = 0.f;
     int hit = 0;  // 0 none, 1 sl, 2 tp
-    const auto tp_ge = [&](float px) {  // long take-profit trigger
+    // fill model: one draw per leg per bar; a leg whose draw fails is
+    // invisible to the whole walk on this bar (gap checks included) and
+    // is tried again on the next bar with that bar's draws
+    bool sl_on = true, tp_on = true;
+    if (fill_on) {
+      sl_on = fill_fires(K, n, t, FCH_STOP, K.fill_thr_stop);
+      tp_on = fill_fires(K, n, t, FCH_LIMIT, K.fill_thr_limit);
+    }
+    const auto tp_ge_raw = [&](float px) {  // long take-profit trigger
       return lim == LIM_TOUCH ? px >= tp : px > tp;
     };
-    const auto tp_le = [&](float px) {  // short take-profit trigger
+    const auto tp_le_raw = [&](float px) {  // short take-profit trigger
       return lim == LIM_TOUCH ? px <= tp : px < tp;
     };
+    const auto tp_ge = [&](float px) { return tp_on && tp_ge_raw(px); };
+    const auto tp_le = [&](float px) { return tp_on && tp_le_raw(px); };
+    const auto sl_le = [&](float px) { return sl_on && px <= sl; };  // long stop
+    const auto sl_ge = [&](float px) { return sl_on && px >= sl; };  // short stop
+    if (!sl_on && (is_long ? (o_px <= sl || l_px <= sl)
+                           : (o_px >= sl || h_px >= sl)))
+      fdiag[FD_BRACKET_SL_MISSES] += 1;
+    if (!tp_on && (is_long ? (tp_ge_raw(o_px) || tp_ge_raw(h_px))
+                           : (tp_le_raw(o_px) || tp_le_raw(l_px))))
+      fdiag[FD_BRACKET_TP_MISSES] += 1;
     const float tp_gap_trig = (lim == LIM_CONSERVATIVE) ? tp : o_px;
     if (K.collision_policy == COLL_WORST) {
       if (is_long) {
-        if (o_px <= sl) { hit = 1; trig = o_px; }
-        else if (l_px <= sl) { hit = 1; trig = sl; }
+        if (sl_le(o_px)) { hit = 1; trig = o_px; }
+        else if (sl_le(l_px)) { hit = 1; trig = sl; }
         else if (tp_ge(o_px)) { hit = 2; trig = tp_gap_trig; }
         else if (tp_ge(h_px)) { hit = 2; trig = tp; }
       } else {
-        if (o_px >= sl) { hit = 1; trig = o_px; }
-        else if (h_px >= sl) { hit = 1; trig = sl; }
+        if (sl_ge(o_px)) { hit = 1; trig = o_px; }
+        else if (sl_ge(h_px)) { hit = 1; trig = sl; }
         else if (tp_le(o_px)) { hit = 2; trig = tp_gap_trig; }
         else if (tp_le(l_px)) { hit = 2; trig = tp; }
       }
@@ -303,18 +351,18 @@ GFX_DEV void env_step_one(const EnvPtrs& P, const EnvParamsK& K, const int n,
       const bool low_first = (K.collision_policy == COLL_ADAPTIVE)
                                  ? (c_px >= o_px)  // up bar: dip printed first
                                  : false;          // ohlc: high before low
-      if (is_long && o_px <= sl) { hit = 1; trig = o_px; }
-      else if (!is_long && o_px >= sl) { hit = 1; trig = o_px; }
+      if (is_long && sl_le(o_px)) { hit = 1; trig = o_px; }
+      else if (!is_long && sl_ge(o_px)) { hit = 1; trig = o_px; }
       else if (is_long && tp_ge(o_px)) { hit = 2; trig = tp_gap_trig; }
       else if (!is_long && tp_le(o_px)) { hit = 2; trig = tp_gap_trig; }
       else {
         for (int k = 0; k < 2 && !hit; ++k) {
           if ((k == 0) == low_first) {  // at the bar low
-            if (is_long) { if (l_px <= sl) { hit = 1; trig = sl; } }
+            if (is_long) { if (sl_le(l_px)) { hit = 1; trig = sl; } }
             else if (tp_le(l_px)) { hit = 2; trig = tp; }
           } else {                      // at the bar high
             if (is_long) { if (tp_ge(h_px)) { hit = 2; trig = tp; } }
-            else if (h_px >= sl) { hit = 1; trig = sl; }
+            else if (sl_ge(h_px)) { hit = 1; trig = sl; }
           }
         }
       }
@@ -589,11 +637,12 @@ GFX_DEV void env_step_one(const EnvPtrs& P, const EnvParamsK& K, const int n,
   if ((K.flags & F_AUTORESET) && P.terminated[n]) reset_env(P, K, n);
 }
 
+template <bool FILL>
 __global__ void env_step_kernel(const EnvPtrs P, const EnvParamsK K,
                                 const int env_lo, const int env_cnt) {
   const int n = env_lo + blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= env_lo + env_cnt) return;
-  env_step_one(P, K, n, env_lo);
+  env_step_one<FILL>(P, K, n, env_lo);
 }
 
 // ---------------------------------------------------------------------------
@@ -769,13 +818,14 @@ __global__ void build_obs_env_kernel(const EnvPtrs P, const EnvParamsK K,
 // launch (~9 us) does not cover the lost width.  Kept behind fuse_obs
 // (default off) with a bitwise-equality GPU test, same as fused_rollout.
 // ---------------------------------------------------------------------------
+template <bool FILL>
 __global__ void env_step_obs_kernel(const EnvPtrs P, const EnvParamsK K,
                                     const int env_lo, const int env_cnt) {
   const int wpb = blockDim.x >> 6;  // waves per block
   const int n = env_lo + blockIdx.x * wpb + ((int)threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const bool valid = n < env_lo + env_cnt;
-  if (valid && lane == 0) env_step_one(P, K, n, env_lo);
+  if (valid && lane == 0) env_step_one<FILL>(P, K, n, env_lo);
   __syncthreads();  // step-phase global writes visible before the obs reads
   if (valid)
     for (int j = lane; j < K.obs_dim; j += 64) build_obs_one(P, K, n, j);
@@ -787,8 +837,12 @@ void launch_env_step(const EnvPtrs& P, const EnvParamsK& K, int env_lo,
   // smaller blocks spread the waves over 4x more CUs.
   const int block = 64;
   const int grid = (env_cnt + block - 1) / block;
-  hipLaunchKernelGGL(env_step_kernel, dim3(grid), dim3(block), 0, stream, P, K,
-                     env_lo, env_cnt);
+  if (K.flags & F_FILL_MODEL)
+    hipLaunchKernelGGL(env_step_kernel<true>, dim3(grid), dim3(block), 0,
+                       stream, P, K, env_lo, env_cnt);
+  else
+    hipLaunchKernelGGL(env_step_kernel<false>, dim3(grid), dim3(block), 0,
+                       stream, P, K, env_lo, env_cnt);
 }
 
 void launch_build_obs(const EnvPtrs& P, const EnvParamsK& K, int env_lo,
@@ -815,8 +869,12 @@ void launch_env_step_obs(const EnvPtrs& P, const EnvParamsK& K, int env_lo,
   const int block = 256;  // 4 envs (waves) per block
   const int wpb = block / 64;
   const int grid = (env_cnt + wpb - 1) / wpb;
-  hipLaunchKernelGGL(env_step_obs_kernel, dim3(grid), dim3(block), 0, stream,
-                     P, K, env_lo, env_cnt);
+  if (K.flags & F_FILL_MODEL)
+    hipLaunchKernelGGL(env_step_obs_kernel<true>, dim3(grid), dim3(block), 0,
+                       stream, P, K, env_lo, env_cnt);
+  else
+    hipLaunchKernelGGL(env_step_obs_kernel<false>, dim3(grid), dim3(block), 0,
+                       stream, P, K, env_lo, env_cnt);
 }
 
 }  // namespace gymfx

@@ -30,6 +30,7 @@ F_STAGEB_PENALTY = 1 << 13
 F_AUTORESET = 1 << 14
 F_FINANCING = 1 << 15
 F_PREFLIGHT = 1 << 16
+F_FILL_MODEL = 1 << 17
 
 _SCALING = {"none": 0, "rolling_zscore": 1, "expanding_zscore": 2}
 
@@ -70,6 +71,8 @@ def _flags(p: EnvParams) -> int:
         f |= F_FINANCING
     if p.enforce_margin_preflight:
         f |= F_PREFLIGHT
+    if p.fill_model_on:
+        f |= F_FILL_MODEL
     return f
 
 
@@ -105,6 +108,11 @@ def pack_params(p: EnvParams, T: int):
         "off_agent": off("agent_state"),
         "off_fc": off("force_close"),
         "off_cal": off("calendar"),
+        # fill model: exact integers (seed as unsigned 64-bit)
+        "fill_seed": p.fill_random_seed & 0xFFFFFFFFFFFFFFFF,
+        "fill_thr_limit": p.fill_thr_limit,
+        "fill_thr_stop": p.fill_thr_stop,
+        "fill_thr_slip": p.fill_thr_slip,
     }
     fparams = {
         "initial_cash": p.initial_cash,
@@ -141,6 +149,7 @@ def pack_params(p: EnvParams, T: int):
         "feature_clip": p.feature_clip,
         "overlay_threshold": p.event_context_no_trade_threshold,
         "margin_init_rate": p.margin_init_rate,
+        "fill_slip_rate": p.fill_slip_rate,
     }
     return iparams, fparams
 

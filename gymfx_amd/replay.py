@@ -33,6 +33,28 @@ def _hash_events(events: List[Dict[str, Any]]) -> str:
     return hashlib.sha256(payload).hexdigest()
 
 
+_M64 = (1 << 64) - 1
+_GOLDEN = 0x9E3779B97F4A7C15
+
+
+def _mix64(x: int) -> int:
+    """splitmix64 finalizer on Python integers (mod 2^64)."""
+    x = (x + _GOLDEN) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def fill_key(seed: int, n: int, t: int, ch: int) -> int:
+    """Fill-model draw key of (seed, env index, market row, channel)."""
+    env_key = _mix64((seed & _M64) ^ ((n * _GOLDEN) & _M64))
+    return _mix64(env_key ^ ((t << 2) | ch))
+
+
+def fill_u53(seed: int, n: int, t: int, ch: int) -> int:
+    return fill_key(seed, n, t, ch) >> 11
+
+
 @dataclass
 class ScalarLedger:
     """Independent average-price position ledger (pure Python scalars)."""
@@ -52,6 +74,13 @@ class ScalarLedger:
     latency_bars: int = 0
     margin_model: int = 0         # 0 leveraged, 1 standard
     margin_init_rate: float = 0.03
+    # seeded fill model (channels: 0 limit, 1 stop, 2 close slip, 3 open slip)
+    prob_fill_on_limit: float = 1.0
+    prob_fill_on_stop: float = 1.0
+    prob_slippage: float = 0.0
+    fill_slip_rate: float = 0.0
+    fill_random_seed: int = 0
+    env_index: int = 0
 
     cash: float = field(init=False)
     pos: float = field(init=False, default=0.0)
@@ -69,9 +98,22 @@ class ScalarLedger:
     pend_tp: float = field(init=False, default=0.0)
     pend_wait: int = field(init=False, default=0)
     events: List[Dict[str, Any]] = field(init=False, default_factory=list)
+    sl_fill_misses: int = field(init=False, default=0)
+    tp_fill_misses: int = field(init=False, default=0)
+    market_fill_slips: int = field(init=False, default=0)
 
     def __post_init__(self):
         self.cash = self.initial_cash
+        self._thr = [int(p * (1 << 53)) for p in
+                     (self.prob_fill_on_limit, self.prob_fill_on_stop,
+                      self.prob_slippage, self.prob_slippage)]
+        self._fill_model_on = self._thr != [1 << 53, 1 << 53, 0, 0]
+
+    def _fires(self, bar: int, ch: int) -> bool:
+        """One fill-model draw for this env on market row ``bar``."""
+        if not self._fill_model_on:
+            return ch < 2  # legs always fill, market orders never slip
+        return fill_u53(self.fill_random_seed, self.env_index, bar, ch) < self._thr[ch]
 
     # -- fills ----------------------------------------------------------
     def _close(self, fill: float, bar: int, kind: str) -> None:
@@ -110,25 +152,43 @@ class ScalarLedger:
             self.br_sl, self.br_tp = self.pend_sl, self.pend_tp
 
     # -- one bar ---------------------------------------------------------
-    def _bracket_trigger(self, o: float, h: float, low: float, c: float):
+    def _bracket_trigger(self, bar: int, o: float, h: float, low: float,
+                         c: float):
         """(trigger_price, kind) for the first bracket child hit this bar,
         honoring the collision and limit-fill policies (mirrors
-        env_step.hip section 2 and reference_step.py)."""
+        env_step.hip section 2 and reference_step.py).  Under the fill
+        model each leg draws once per bar; a leg that fails its draw does
+        not exist for this bar's walk and a trigger it would have had is
+        counted as a miss."""
         is_long = self.pos > 0
         sl, tp = self.br_sl, self.br_tp
         lim = self.limit_fill_policy
+        sl_live = self._fires(bar, 1)
+        tp_live = self._fires(bar, 0)
 
-        def tp_hit(px: float) -> bool:
+        def tp_touch(px: float) -> bool:
             if is_long:
                 return px >= tp if lim == 0 else px > tp
             return px <= tp if lim == 0 else px < tp
 
+        def tp_hit(px: float) -> bool:
+            return tp_live and tp_touch(px)
+
+        def sl_hit(px: float) -> bool:
+            return sl_live and (px <= sl if is_long else px >= sl)
+
+        adverse, favourable = (low, h) if is_long else (h, low)
+        if not sl_live and (adverse <= sl if is_long else adverse >= sl):
+            self.sl_fill_misses += 1
+        if not tp_live and (tp_touch(o) or tp_touch(favourable)):
+            self.tp_fill_misses += 1
+
         tp_gap_px = tp if lim == 2 else o  # conservative: no improvement
-        sl_gap = o <= sl if is_long else o >= sl
+        sl_gap = sl_hit(o)
         if self.collision_policy == 0:  # worst_case: stop absolute priority
             if sl_gap:
                 return o, "bracket_sl_fill"
-            if (low <= sl) if is_long else (h >= sl):
+            if sl_hit(adverse):
                 return sl, "bracket_sl_fill"
             if tp_hit(o):
                 return tp_gap_px, "bracket_tp_fill"
@@ -143,31 +203,41 @@ class ScalarLedger:
         low_first = (c >= o) if self.collision_policy == 2 else False
         for at_low in ((True, False) if low_first else (False, True)):
             if at_low:
-                if is_long and low <= sl:
+                if is_long and sl_hit(low):
                     return sl, "bracket_sl_fill"
                 if not is_long and tp_hit(low):
                     return tp, "bracket_tp_fill"
             else:
                 if is_long and tp_hit(h):
                     return tp, "bracket_tp_fill"
-                if not is_long and h >= sl:
+                if not is_long and sl_hit(h):
                     return sl, "bracket_sl_fill"
         return None, None
 
     def step(self, bar: int, o: float, h: float, low: float, c: float,
              action: int) -> None:
         slip = self.slippage
-        buy = lambda px: px * (1.0 + slip)     # noqa: E731
-        sell = lambda px: px * (1.0 - slip)    # noqa: E731
+        buy = lambda px, s=slip: px * (1.0 + s)     # noqa: E731
+        sell = lambda px, s=slip: px * (1.0 - s)    # noqa: E731
         # 1. pending market fills at open (latency holds them in transit)
         if self.pend_wait > 0 and (self.pend_close or self.pend_dir != 0):
             self.pend_wait -= 1
         else:
+            # a delivered market order pays fill_slip_rate on top when
+            # its slippage draw fires (close: channel 2, open: channel 3)
             if self.pend_close and self.pos != 0:
-                fill = buy(o) if self.pos < 0 else sell(o)
+                s = slip
+                if self._fires(bar, 2):
+                    s += self.fill_slip_rate
+                    self.market_fill_slips += 1
+                fill = buy(o, s) if self.pos < 0 else sell(o, s)
                 self._close(fill, bar, "order_filled")
             if self.pend_dir != 0 and self.pos == 0:
-                fill = buy(o) if self.pend_dir > 0 else sell(o)
+                s = slip
+                if self._fires(bar, 3):
+                    s += self.fill_slip_rate
+                    self.market_fill_slips += 1
+                fill = buy(o, s) if self.pend_dir > 0 else sell(o, s)
                 self._open(self.pend_dir, self.position_size, fill, bar)
             self.pend_close = False
             self.pend_dir = 0
@@ -175,7 +245,7 @@ class ScalarLedger:
             self.pend_wait = 0
         # 2. bracket children per collision/limit policy
         if self.br_active and not self.br_armed and self.pos != 0:
-            trig, kind = self._bracket_trigger(o, h, low, c)
+            trig, kind = self._bracket_trigger(bar, o, h, low, c)
             if trig is not None:
                 fill = sell(trig) if self.pos > 0 else buy(trig)
                 self._close(fill, bar, kind)
@@ -232,6 +302,12 @@ class ReplayAdapter:
             latency_bars=p.latency_bars,
             margin_model=p.margin_model,
             margin_init_rate=p.margin_init_rate,
+            prob_fill_on_limit=p.prob_fill_on_limit,
+            prob_fill_on_stop=p.prob_fill_on_stop,
+            prob_slippage=p.prob_slippage,
+            fill_slip_rate=p.fill_slip_rate,
+            fill_random_seed=p.fill_random_seed,
+            env_index=0,
         )
         o = market_data.columns["OPEN"]
         h = market_data.columns["HIGH"]
@@ -271,12 +347,20 @@ class ReplayAdapter:
             ("equity", "cash", "commission_paid", "position")
         }
         recon["trade_count"] = engine["trade_count"] == oracle["trade_count"]
+        fill_engine = env.fill_model_diagnostics(0)
+        fill_oracle = {
+            "bracket_sl_fill_misses": ledger.sl_fill_misses,
+            "bracket_tp_fill_misses": ledger.tp_fill_misses,
+            "market_fill_slips": ledger.market_fill_slips,
+        }
+        recon["fill_model"] = fill_engine == fill_oracle
         result = {
             "schema": "gymfx.replay.v1",
             "steps": n_steps,
             "last_bar": last_bar,
             "engine": engine,
             "oracle": oracle,
+            "fill_model": {"engine": fill_engine, "oracle": fill_oracle},
             "reconciled": all(recon.values()),
             "reconciliation": recon,
             "events": ledger.events,

@@ -150,7 +150,11 @@ class TargetReplay:
     def __init__(self, profile: ExecutionCostProfile,
                  fill_model: Optional[FillModel] = None):
         self.profile = profile
-        self.fill = fill_model or FillModel(random_seed=profile.random_seed)
+        self.fill = fill_model or FillModel(
+            random_seed=profile.random_seed,
+            prob_fill_on_limit=profile.prob_fill_on_limit,
+            prob_fill_on_stop=profile.prob_fill_on_stop,
+            prob_slippage=profile.prob_slippage)
 
     # -- helpers --------------------------------------------------------
     def _points(self, frame: MarketFrame, long: bool) -> Tuple[Decimal, ...]:
